@@ -1,9 +1,13 @@
 #!/usr/bin/env python
 """Benchmark: multi-scale SWE-GNN rollout throughput on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload zenodo4]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload zenodo4] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run does what the headline figure needs and nothing else: build the workload and its
+plan, W warmup steps, K timed steps, the outputs of the last timed step to DIR/<name>.npy when
+--dump-outputs is given, the result line.  --full adds every other record described below.
 
 One "step" = one full T=48 autoregressive rollout (rollout_test semantics) of one simulation
 per rank, with inputs resident in HBM, through the HIP engine (fused msw_rollout: the T
@@ -12,7 +16,8 @@ sim per GPU, seed = rank); at N>1 each step ends with ONE RCCL all-gather of the
 rollouts (the north star's end-of-rollout collective).  Throughput = all ranks' fine-scale
 nodes x rollout steps / max-over-ranks wall time.
 
-Rank 0 also reports:
+With --full rank 0 also reports (and, at N > 1, the strong-scaling, RCCL single-mesh
+decomposition and DDP training records of run_extras):
   roofline      -- the aggregation (hop) kernel at the finest scale, timed live with HIP
                    events on the stream it is launched on, algorithmic bytes per launch
                    E*(4F+4) + N*(12F+4) (SURVEY §8(d)), peak 8 TB/s;
@@ -275,6 +280,37 @@ def rank_batch(workload, ids, T, cache=None):
 def _sync(dev):
     if dev.type == "cuda":
         torch.cuda.synchronize(dev)
+
+
+DUMP_LIMIT_BYTES = 64 * 10 ** 6  # --dump-outputs: all files of one run together
+NPY_HEADERS_BYTES = 4096         # room kept for an array's .npy headers (<name>, <name>_rows)
+
+
+def dump_outputs(path, arrays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: every tensor of `arrays` (name -> tensor) as path/<name>.npy in float32
+    (float64 tensors stay float64).  An array over its share of `limit` is written as a fixed
+    sample of its leading-dimension rows (numpy default_rng(0), ascending; the same rows for
+    the same shape in every run and build), the chosen rows beside it as <name>_rows.npy
+    (float64).  -> {name: {"shape", "dtype", "sampled_rows"}}."""
+    os.makedirs(path, exist_ok=True)
+    share = limit // max(len(arrays), 1) - NPY_HEADERS_BYTES
+    rec = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.dtype != torch.float64:
+            t = t.float()
+        rows = int(t.shape[0])
+        row_bytes = t[0].numel() * t.element_size() if rows else 0
+        sampled = None
+        if rows * row_bytes > share:
+            sampled = share // (row_bytes + 8)  # + the row's own index in <name>_rows.npy
+            idx = np.sort(np.random.default_rng(0).choice(rows, sampled, replace=False))
+            t = t.index_select(0, torch.from_numpy(idx).to(t.device))
+            np.save(os.path.join(path, name + "_rows.npy"), idx.astype(np.float64))
+        a = t.cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), a)
+        rec[name] = {"shape": list(a.shape), "dtype": str(a.dtype), "sampled_rows": sampled}
+    return rec
 
 
 def make_runner(workload, ids, T, dev, engine, cache):
@@ -588,6 +624,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="zenodo4", choices=sorted(WORKLOADS))
     ap.add_argument("--T", type=int, default=48)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (rank 0's "
+                         "rollout [nodes, 2, T]) as DIR/rollout.npy, float32, at most 64 MB (a fixed "
+                         "seeded sample of rows of a larger one)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure: the roofline "
+                         "records, the parity against the stored reference rollout and the CPU "
+                         "reference, the CPU baseline, the reference-loop caller's own cost and, at "
+                         "N > 1, the strong-scaling / RCCL decomposition / DDP records")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--no-roofline-large", action="store_true",
@@ -695,8 +740,10 @@ def main():
                     preds.append(pred)
             return torch.stack(preds, -1)
 
+    last = [None]  # what the latest step returned to its caller (--dump-outputs)
+
     def one_step():
-        r = rollout()
+        r = last[0] = rollout()
         if world > 1:
             gather(r[:n0] if fine_rows is None else r.index_select(0, fine_rows))
 
@@ -730,8 +777,12 @@ def main():
         nodes_all = float(tn.item())
     value = nodes_all * T * args.steps / dt
 
+    dumped = None
+    if args.dump_outputs and rank == 0 and last[0] is not None:
+        dumped = dump_outputs(args.dump_outputs, {"rollout": last[0]})
+
     caller_overhead = None
-    if args.caller == "reference-loop" and world == 1:
+    if args.full and args.caller == "reference-loop" and world == 1:
         # the caller's own cost: the same loop with the model replaced by a stub that returns a
         # fresh [N, 2] tensor (no GPU work): its index_put / slice copy / cat kernels and its
         # per-step host synchronisation (check_type_BC reads the GPU tensor type_BC)
@@ -751,6 +802,7 @@ def main():
     result = None
     if rank == 0:
         st = plan.stats()
+    if rank == 0 and args.full:
         # ---------------- roofline: aggregation (hop) kernel at the finest scale
         F = desc["hid_features"]
         t_hop, (rows, edges) = time_kernel(plan, "hop", 0)
@@ -932,6 +984,7 @@ def main():
                                              for t in range(Tc)))}
         except Exception as e:  # noqa: BLE001
             cpu = {"error": repr(e)}
+    if rank == 0:
         result = {
             "metric": "mesh-nodes x rollout-steps / sec (fine-scale nodes); fp32 max-abs err vs CPU ref",
             "value": value, "unit": "fine-node-steps/s", "n_gpus": world, "steps": args.steps,
@@ -952,7 +1005,7 @@ def main():
             "library": dict(_lib.lib_info(), built_from_current_sources=_built_from_sources()),
             "msw_env": msw_env(),
             "all_node_steps_per_s": value * desc.get("batch_nodes", desc["all_nodes"]) / fine_rank,
-            "roofline": roof, "cpu_baseline": cpu, "parity": parity,
+            "full": args.full,
             "engine": {"kernels_per_step": st["kernels_per_step"], "graph_captured": st["graph_captured"],
                        "device_bytes": st["device_bytes"],
                        "device_bytes_note": "plan-owned: graph tables, weights, per-node buffers and the "
@@ -964,9 +1017,13 @@ def main():
                                      "setup; first_rollout_s = the first warmup rollout incl. its "
                                      "hipGraph capture"},
         }
+        if args.full:
+            result.update({"roofline": roof, "cpu_baseline": cpu, "parity": parity})
+        if dumped is not None:
+            result["dumped_outputs"] = dumped
         if caller_overhead is not None:
             result["caller_overhead"] = caller_overhead
-    if world > 1:
+    if world > 1 and args.full:
         # the north star's strong scaling (fixed config-3 sets, rank 0 alone vs all ranks with
         # the RCCL all-gather), the RCCL single-mesh decomposition and DDP training: after the
         # weak line's timed region and its rank-0 records, inside --extras-budget, never fatal
@@ -975,6 +1032,7 @@ def main():
         extras = run_extras(dist, rank, world, dev, args, cpu_barrier, backend, group=cpu_group)
         if rank == 0:
             result.update(extras)
+    if world > 1:
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:

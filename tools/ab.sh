@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B timing of engine variants on the GPU box: one bench run per environment setting.
-#   bash tools/ab.sh "" "MSW_POOL_FUSE=0" "MSW_UNPOOL_FUSE=0" [-- bench args]
+#   bash tools/ab.sh "" "MSW_POOL_FUSE=0" "MSW_UNPOOL_FUSE=0" [-- --full and other bench args]
 # Each run has its own time limit; a failure stops the script.
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 mkdir -p gpurun_out
@@ -9,7 +9,8 @@ while [ $# -gt 0 ]; do
   if [ "$1" == "--" ]; then shift; args=("$@"); break; fi
   envs+=("$1"); shift
 done
-[ ${#args[@]} -eq 0 ] && args=(--no-cpu-baseline --steps 10 --warmup 3)
+# --full: the log line below reads the roofline and parity records
+[ ${#args[@]} -eq 0 ] && args=(--full --no-cpu-baseline --steps 10 --warmup 3)
 [ -z "${AB_KEEP:-}" ] && : > gpurun_out/ab.log
 for e in "${envs[@]}"; do
   env $e timeout -k 10 300 python bench.py "${args[@]}" > gpurun_out/ab_run.json 2> gpurun_out/ab_run.err

@@ -1,4 +1,4 @@
-"""Thread sweep of the CPU baseline (bench.py cpu_baseline): the oracle's rollout of one
+"""Thread sweep of the CPU baseline (bench.py --full cpu_baseline): the oracle's rollout of one
 zenodo4 simulation (the reference's algorithm, same ATen CPU ops) at 1 / 8 / 16 / 32 / 64
 host threads (and all of them on hosts of at most 64 cores), fine-node-steps/s each.  Why bench.py caps the baseline at 16 threads: the
 GPU box gives one GPU a 16-thread CPU share, and the rate does not grow past it.

@@ -8,7 +8,7 @@ coalesced reads -> read bytes = 2 x FETCH_SIZE x 1024; WRITE_SIZE (KB) is exact 
 16-B/lane stores.  Infinity-Cache hits are counted too (memory-side L2 requests), so at
 sizes that fit the 256 MB L3 this is L2-miss traffic, an upper bound on HBM bytes.
 "key" entries: the fine-scale middle hop (the bench roofline kernel) = the k_hop grid with
-the most dispatches (bench.py times it 200+ times).
+the most dispatches (bench.py --full times it 200+ times: profile that command).
 """
 import csv
 import glob

@@ -1,5 +1,5 @@
-"""Cross-check bench.py's live roofline timing against the rocprofv3 kernel trace of the
-same command: bench.py times back-to-back launches of one kernel with HIP events
+"""Cross-check bench.py --full's live roofline timing against the rocprofv3 kernel trace of
+the same command: bench.py --full times back-to-back launches of one kernel with HIP events
 (msw_bench_kernel); this finds those runs in the trace (>= 20 consecutive launches of one
 kernel name) and reports their average duration and their launch-to-launch period (what
 the HIP events measure: duration + boundary).
