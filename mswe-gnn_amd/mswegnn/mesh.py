@@ -29,7 +29,7 @@ import numpy as np
 import torch
 
 __all__ = ["Graph", "make_multiscale_mesh", "make_single_scale_mesh", "wet_state",
-           "mesh_config", "config3_members"]
+           "mesh_config", "config3_members", "irregularize"]
 
 
 class Graph:
@@ -335,3 +335,205 @@ def mesh_config(name):
         "hbm1m": dict(n_coarse=177, num_scales=3),    # N0 = 1,002,529
     }
     return table[name]
+
+
+# ----------------------------------------------------------------------------- irregular meshes
+_EXTRAS = ("childless", "children16", "children17", "two_parents", "isolated", "ghost_first")
+
+
+def irregularize(graph, seed, *, move=0.3, orphan=0.03, delete=0.03, permute=True, order="canonical",
+                 extra=()):
+    """Turn a quadtree mesh of :func:`make_multiscale_mesh` / :func:`make_single_scale_mesh`
+    (optionally after :func:`wet_state`) into one with the irregularities of the reference's
+    real meshes (database/graph_creation.py:422-436, 498-518, 922-927): 0..n children per
+    coarse face, fine faces without a parent, deleted fine faces, arbitrary face numbering.
+    Returns ``(Graph, old_of_new)``; ``old_of_new[k]`` is the input row of output row ``k``.
+
+    Structural edits, drawn from a generator of their own (``permute``, ``order`` and ``extra``
+    never change them, so one ``seed`` is one edited mesh under every labelling), in this order:
+
+    * ``delete``: that share of the finest faces (never the BC face or a ghost) goes, with its
+      row, both directions of its dual edges and its intra edge;
+    * ``move``: on every level that share of the (coarse, fine) pairs is re-assigned to a dual
+      neighbour of the pair's coarse face (never a ghost; the ghost->ghost pair stays);
+    * ``orphan``: on every level that share of the pairs is dropped (the fine face has no parent).
+
+    ``extra`` names single structures, applied after the random edits without any draw, in the
+    order of this list ("first" = lowest input row):
+
+    * ``"childless"``: the SECOND non-ghost coarse face of level 0 hands all its children to its
+      first non-ghost dual neighbour;
+    * ``"children16"`` / ``"children17"``: the FIRST non-ghost coarse face of level 0 ends with
+      exactly that many children: pairs of the first finest faces that are not its children (nor
+      the ghost) are re-assigned to it (parentless ones get a pair appended); a surplus is dropped;
+    * ``"two_parents"``: the first non-ghost face of scale 1 with exactly one parent gets a second
+      pair (appended to level 1) with that parent's first non-ghost dual neighbour;
+    * ``"isolated"``: the first surviving finest face with three in-edges that is neither the BC
+      face nor a ghost loses every dual edge, both directions (in-degree 0, row kept);
+    * ``"ghost_first"``: a labelling, not an edit: the finest ghost becomes the first row of its
+      scale (``node_BC`` follows).
+
+    Labelling: ``permute=True`` permutes the faces inside each scale, ghosts stay last in their
+    scale; ``permute=False`` keeps the surviving rows in input order.  Edge order:
+    ``order="canonical"`` sorts each scale's dual edges by (row, col) with the ghost->BC edge
+    last and each level's intra edges coarse-major, fine-ascending (what ``to_undirected`` and
+    the reference's ``np.where`` give); ``order="kept"`` leaves every surviving edge column where
+    it was (appended pairs last), so ids change but each destination's in-edge order does not.
+    ``x``, ``y``, ``area``, ``edge_attr``, the pointers and ``node_BC`` follow; ``BC``,
+    ``type_BC`` and ``edge_BC_length`` are unchanged.
+    """
+    if order not in ("canonical", "kept"):
+        raise ValueError("order is 'canonical' or 'kept'")
+    extra = tuple(extra)
+    for name in extra:
+        if name not in _EXTRAS:
+            raise ValueError(f"unknown extra {name!r}")
+    if "children16" in extra and "children17" in extra:
+        raise ValueError("children16 and children17 name the same coarse face")
+    multi = "node_ptr" in graph
+    N, E = int(graph.x.shape[0]), int(graph.edge_index.shape[1])
+    nptr = graph.node_ptr.numpy().astype(np.int64) if multi else np.array([0, N], np.int64)
+    eptr = graph.edge_ptr.numpy().astype(np.int64) if multi else np.array([0, E], np.int64)
+    S = len(nptr) - 1
+    ei = graph.edge_index.numpy().astype(np.int64)
+    ghosts = nptr[1:] - 1 if multi else graph.node_BC.numpy().astype(np.int64)[:1]
+    if multi and S > 1:
+        iptr = graph.intra_edge_ptr.numpy().astype(np.int64)
+        iei = graph.intra_mesh_edge_index.numpy().astype(np.int64)
+        levels = [iei[:, iptr[l]:iptr[l + 1]].copy() for l in range(S - 1)]
+    else:
+        levels = []
+    is_ghost = np.zeros(N, bool)
+    is_ghost[ghosts] = True
+    nbrs = {}  # non-ghost dual neighbours of every face, in edge order (input ids)
+    for r, c in ei.T:
+        if not is_ghost[r] and not is_ghost[c]:
+            nbrs.setdefault(int(r), []).append(int(c))
+
+    # ---- structural edits (input ids) ----
+    rng = np.random.default_rng([int(seed), 0])
+    keep_node = np.ones(N, bool)
+    keep_edge = np.ones(E, bool)
+    bc_faces = ei[1][is_ghost[ei[0]]]
+    cand = np.arange(nptr[0], nptr[1])
+    cand = cand[~is_ghost[cand] & ~np.isin(cand, bc_faces)]
+    gone = rng.choice(cand, size=int(round(delete * len(cand))), replace=False)
+    keep_node[gone] = False
+    keep_edge &= keep_node[ei[0]] & keep_node[ei[1]]
+    for l in range(len(levels)):
+        pairs = levels[l][:, keep_node[levels[l][1]]]
+        free = np.nonzero(~is_ghost[pairs[0]])[0]  # every pair but ghost -> ghost
+        for k in rng.choice(free, size=int(round(move * len(free))), replace=False):
+            opts = nbrs.get(int(pairs[0, k]), [])
+            if opts:
+                pairs[0, k] = opts[int(rng.integers(len(opts)))]
+        drop = rng.choice(free, size=int(round(orphan * len(free))), replace=False)
+        keep = np.ones(pairs.shape[1], bool)
+        keep[drop] = False
+        levels[l] = pairs[:, keep]
+
+    # ---- named single structures (no draws) ----
+    def coarse_faces(l):
+        return [int(v) for v in range(nptr[l + 1], nptr[l + 2]) if not is_ghost[v]]
+
+    if "childless" in extra:
+        c = coarse_faces(0)[1]
+        levels[0][0, levels[0][0] == c] = nbrs[c][0]
+    for name, want in (("children16", 16), ("children17", 17)):
+        if name not in extra:
+            continue
+        c = coarse_faces(0)[0]
+        pairs = levels[0]
+        mine = np.nonzero(pairs[0] == c)[0]
+        if len(mine) > want:
+            keep = np.ones(pairs.shape[1], bool)
+            keep[mine[want:]] = False
+            pairs = pairs[:, keep]
+        have = set(pairs[1, pairs[0] == c].tolist())
+        need = want - len(have)
+        for f in range(nptr[0], nptr[1]):
+            if need == 0:
+                break
+            if is_ghost[f] or not keep_node[f] or f in have:
+                continue
+            at = np.nonzero(pairs[1] == f)[0]
+            if len(at):
+                pairs[0, at[0]] = c
+            else:
+                pairs = np.concatenate([pairs, [[c], [f]]], 1)
+            need -= 1
+        assert need == 0, "mesh too small for " + name
+        levels[0] = pairs
+    if "two_parents" in extra:
+        pairs = levels[1]
+        for f in range(nptr[1], nptr[2]):
+            at = np.nonzero(pairs[1] == f)[0]
+            if is_ghost[f] or len(at) != 1:
+                continue
+            second = [v for v in nbrs[int(pairs[0, at[0]])] if v != pairs[0, at[0]]]
+            levels[1] = np.concatenate([pairs, [[second[0]], [f]]], 1)
+            break
+        else:
+            raise ValueError("no face of scale 1 with exactly one parent")
+    if "isolated" in extra:
+        live = keep_edge & (ei[1] < nptr[1]) & (ei[1] >= nptr[0])
+        deg = np.bincount(ei[1][live], minlength=N)
+        f = next(int(v) for v in range(nptr[0], nptr[1])
+                 if keep_node[v] and not is_ghost[v] and v not in bc_faces and deg[v] == 3)
+        keep_edge &= (ei[0] != f) & (ei[1] != f)
+
+    # ---- labelling ----
+    lab = np.random.default_rng([int(seed), 1])
+    old_of_new = []
+    for s in range(S):
+        rows = np.arange(nptr[s], nptr[s + 1])
+        rows = rows[keep_node[rows]]
+        g = rows[is_ghost[rows]]
+        faces = rows[~is_ghost[rows]]
+        if permute:
+            faces = faces[lab.permutation(len(faces))]
+            rows = np.concatenate([faces, g])
+        if s == 0 and "ghost_first" in extra:
+            rows = np.concatenate([g, rows[~is_ghost[rows]]])
+        old_of_new.append(rows)
+    new_nptr = np.cumsum([0] + [len(r) for r in old_of_new])
+    old_of_new = np.concatenate(old_of_new)
+    new_of_old = np.full(N, -1, np.int64)
+    new_of_old[old_of_new] = np.arange(len(old_of_new))
+
+    # ---- edges ----
+    cols, new_eptr = [], [0]
+    for s in range(S):
+        k = np.arange(eptr[s], eptr[s + 1])
+        k = k[keep_edge[k]]
+        if order == "canonical":
+            r, c = new_of_old[ei[0, k]], new_of_old[ei[1, k]]
+            k = k[np.lexsort((c, r, is_ghost[ei[0, k]]))]  # (row, col), the ghost -> BC edge last
+        cols.append(k)
+        new_eptr.append(new_eptr[-1] + len(k))
+    cols = np.concatenate(cols)
+    new_ei = new_of_old[ei[:, cols]]
+    new_levels, new_iptr = [], [0]
+    for pairs in levels:
+        p = new_of_old[pairs]
+        if order == "canonical":
+            p = p[:, np.lexsort((p[1], p[0]))]
+        new_levels.append(p)
+        new_iptr.append(new_iptr[-1] + p.shape[1])
+
+    out = graph.clone()
+    idx = torch.from_numpy(old_of_new)
+    for k in ("x", "y", "area"):
+        if k in graph:
+            setattr(out, k, getattr(graph, k)[idx].clone())
+    out.edge_index = torch.from_numpy(new_ei).to(graph.edge_index.dtype)
+    out.edge_attr = graph.edge_attr[torch.from_numpy(cols)].clone()
+    out.node_BC = torch.from_numpy(new_of_old[graph.node_BC.numpy().astype(np.int64)]).to(graph.node_BC.dtype)
+    if multi:
+        out.node_ptr = torch.from_numpy(new_nptr).to(graph.node_ptr.dtype)
+        out.edge_ptr = torch.from_numpy(np.asarray(new_eptr)).to(graph.edge_ptr.dtype)
+        out.intra_mesh_edge_index = torch.from_numpy(
+            np.concatenate(new_levels, 1) if new_levels else np.zeros((2, 0), np.int64)
+        ).to(graph.intra_mesh_edge_index.dtype)
+        out.intra_edge_ptr = torch.from_numpy(np.asarray(new_iptr)).to(graph.intra_edge_ptr.dtype)
+    return out, old_of_new

@@ -2,8 +2,8 @@
 
 Partitioning is nested across scales: the coarsest scale is cut into W parts (a BFS sweep
 over its dual graph, cut into contiguous chunks balanced by the number of finest-scale
-descendants) and every finer node follows its parent (each fine cell has exactly one
-parent, train.py / dataset.py intra-mesh edges).  Consequences:
+descendants) and every finer node follows its parent (train.py / dataset.py intra-mesh
+edges); a fine cell without a parent follows a dual neighbour.  Consequences:
   * pooling (children -> parent) and unpooling (parent -> children) never cross ranks;
   * the only halo is the scale edges' one: the sources of the in-edges of a rank's owned
     nodes, per scale.  Those rows are refreshed before every launch that gathers from
@@ -98,8 +98,28 @@ def partition_multiscale(graph, parts):
         fine = np.arange(npt[s], npt[s + 1])
         has = parent[fine] >= 0
         owner[fine[has]] = owner[parent[fine[has]]]
-        for v in fine[~has]:  # orphan (not produced by the reference's meshes): nearest owned
-            owner[v] = 0
+        # orphans (a fine face whose centre lies in no coarse face): the owner of the first dual
+        # neighbour that has one, in edge order, so they spread like their neighbourhood instead
+        # of piling up on one rank; orphans next to orphans wait a sweep, an island goes to rank 0
+        todo = list(fine[~has])
+        if todo:  # the scale's in-edges by destination (stable: edge order kept per destination)
+            es = ei[:, ept[s]:ept[s + 1]]
+            by_dst = np.argsort(es[1], kind="stable")
+            dst, src = es[1][by_dst], es[0][by_dst]
+        while todo:
+            left = []
+            for v in todo:
+                a, b = np.searchsorted(dst, (v, v + 1))
+                near = owner[src[a:b]]
+                near = near[near >= 0]
+                if len(near):
+                    owner[v] = near[0]
+                else:
+                    left.append(v)
+            if len(left) == len(todo):
+                owner[left] = 0
+                break
+            todo = left
     return owner
 
 

@@ -9,7 +9,9 @@ fused (un)pooling slot records, and the halo exchange lists of a partitioned mes
 harness checks the invariants the kernels rely on (every edge in exactly one slot, reference
 edge order per destination, records pointing at the right rows, exchange lists row-for-row
 consistent between ranks) on the tiny, small, config-3, batched, degree-16 and partitioned
-meshes; a node with 17 in-edges must be refused with MSW_ERR_UNSUPPORTED.  No GPU.
+meshes, and on irregular, renumbered ones (mswegnn.mesh.irregularize: both edge orders, in a
+batch, partitioned, and its named single structures); a node with 17 in-edges or a coarse face
+with 17 children must be refused with MSW_ERR_UNSUPPORTED.  No GPU.
 """
 import json
 import os
@@ -89,7 +91,8 @@ def harness(tmp_path_factory):
 
 def test_host_plan_construction_under_asan_ubsan(harness, tmp_path):
     from mswegnn.batch import collate
-    from mswegnn.mesh import config3_members, make_multiscale_mesh, mesh_config, make_single_scale_mesh, wet_state
+    from mswegnn.mesh import (config3_members, irregularize, make_multiscale_mesh, mesh_config,
+                              make_single_scale_mesh, wet_state)
     from mswegnn.partition import decompose
     from mswegnn.rollout import adapt_batch_training
     path = tmp_path / "cases.bin"
@@ -111,8 +114,23 @@ def test_host_plan_construction_under_asan_ubsan(harness, tmp_path):
         names.append("degree16")
         _write_case(f, "degree17", _star(17), expect_rc=MSW_ERR_UNSUPPORTED)
         names.append("degree17")
-        for W in (2, 3):
-            g = wet_state(make_multiscale_mesh(**mesh_config("small"), T=2), seed=3)
+        # irregular, renumbered meshes (mswegnn.mesh.irregularize): 0..10 children per coarse face,
+        # orphans, deleted faces, in-degree 0..3, permuted ids, in both edge orders; one in a batch
+        # with a quadtree mesh; the named single structures
+        small = wet_state(make_multiscale_mesh(**mesh_config("small"), T=2), seed=3)
+        for order in ("canonical", "kept"):
+            _write_case(f, f"irr_{order}", irregularize(small, 5, order=order)[0])
+            names.append(f"irr_{order}")
+        _write_case(f, "batch_irr_regular", adapt_batch_training(collate(
+            [irregularize(small, 6)[0], make_multiscale_mesh(n_coarse=2, num_scales=4, seed=1, T=2)])))
+        names.append("batch_irr_regular")
+        for extra in ("childless", "children16", "isolated", "ghost_first", "two_parents"):
+            _write_case(f, extra, irregularize(small, 7, extra=(extra,))[0])
+            names.append(extra)
+        _write_case(f, "children17", irregularize(small, 7, extra=("children17",))[0], expect_rc=MSW_ERR_UNSUPPORTED)
+        names.append("children17")
+        for W, g, tag, gid in [(2, small, "small", 2), (3, small, "small", 3),
+                               (2, irregularize(small, 8)[0], "irr", 12), (3, irregularize(small, 8)[0], "irr", 13)]:
             owner, lps, plan = decompose(g, W)
             for p, lp in enumerate(lps):
                 peers, scales, rptr, rrows, sptr, srows = [], [], [0], [], [0], []
@@ -125,9 +143,9 @@ def test_host_plan_construction_under_asan_ubsan(harness, tmp_path):
                         srows += list(send)
                         rptr.append(len(rrows))
                         sptr.append(len(srows))
-                _write_case(f, f"small_part{p}of{W}", lp.graph, group=W, rank=p,
+                _write_case(f, f"{tag}_part{p}of{W}", lp.graph, group=gid, rank=p,
                             xch=(peers, scales, rptr, rrows, sptr, srows), l2g=lp.nodes)
-                names.append(f"small_part{p}of{W}")
+                names.append(f"{tag}_part{p}of{W}")
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:halt_on_error=1:abort_on_error=0",
                UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
     env.pop("LD_PRELOAD", None) if "libasan" in env.get("LD_PRELOAD", "") else None
@@ -139,13 +157,22 @@ def test_host_plan_construction_under_asan_ubsan(harness, tmp_path):
     assert sorted(by) == sorted(names)
     assert by["degree17"]["rc"] == MSW_ERR_UNSUPPORTED and "16 in-edges" in by["degree17"]["error"]
     assert by["degree16"]["rc"] == 0
+    # 17 children: the pooling tiles hold whole families of at most 16, refused like 17 in-edges
+    assert by["children17"]["rc"] == MSW_ERR_UNSUPPORTED and "16 in-edges" in by["children17"]["error"]
+    assert by["children16"]["rc"] == 0
+    # fused pooling / unpooling stay on for irregular levels; a fine node with two parents drops
+    # the fused unpooling of ITS level only
+    for nm in ("irr_canonical", "irr_kept", "childless", "children16", "isolated", "ghost_first"):
+        assert by[nm]["fused_pool_levels"] == [1, 1, 1] and by[nm]["fused_unpool_levels"] == [1, 1, 1], by[nm]
+    assert by["two_parents"]["fused_unpool_levels"] == [1, 0, 1] and by["two_parents"]["fused_pool_levels"] == [1, 1, 1]
     # the degree-aware destination order never needs more tiles than the graph order
     for x in recs:
         if x.get("rc") == 0 and "ntiles" in x:
             assert all(a <= b for a, b in zip(x["ntiles"], x["ntiles_graph_order"])), x
     # partitions: halo rows exist and both groups' exchange lists are consistent row for row
     groups = {x["group"]: x for x in recs if "group" in x}
-    assert sorted(groups) == [2, 3] and all(x["exchange"] == "consistent" for x in groups.values())
+    assert sorted(groups) == [2, 3, 12, 13] and all(x["exchange"] == "consistent" for x in groups.values())
     assert all(by[f"small_part{p}of3"]["halo_rows"] > 0 for p in range(3))
+    assert all(by[f"irr_part{p}of3"]["halo_rows"] > 0 for p in range(3))
     print(f"{len(by)} host plans clean under ASan + UBSan: " +
           ", ".join(f"{k} {v.get('ntiles', v.get('rc'))}" for k, v in sorted(by.items())))

@@ -100,6 +100,35 @@ def test_oracle_f64_default_width():
     assert_pinned(orc.rollout(P, cfg, g), torch.from_numpy(fx["rollout"]))
 
 
+IRREGULAR = ["fx_irr_tiny_K4_F32_step", "fx_irr_small_K4_F32_rollout48", "fx_irr_small_K4_F32_wet_rollout8"]
+
+
+def irregular_fixture(name):
+    """-> (input graph rebuilt from the manifest's arguments, fixture arrays) of a fixture the
+    reference wrote on an irregular, renumbered mesh (oracle/gen_golden_irregular.py)."""
+    from mswegnn.mesh import irregularize
+    spec = manifest()["fx_irr_spec"][name]
+    g = make_multiscale_mesh(**mesh_config(spec["mesh"]), T=spec["T"])
+    if spec["wet"] is not None:
+        g = wet_state(g, seed=spec["wet"])
+    g = irregularize(g, spec["seed"], order="canonical")[0]
+    fx = golden(name)
+    assert np.array_equal(_digest(g), fx["digest"]), "irregular mesh generator drifted"
+    return g, fx
+
+
+@pytest.mark.parametrize("name", IRREGULAR)
+def test_oracle_irregular_mesh(name):
+    """The reference's own forward / rollout_test (K4_F32) on irregularize()d meshes: 0..10
+    children per coarse face, orphans, deleted finest faces, permuted ids."""
+    g, fx = irregular_fixture(name)
+    cfg = manifest()["weights_K4_F32_cfg"]
+    if "y" in fx:
+        assert_pinned(orc.forward(weights("K4_F32"), cfg, g), torch.from_numpy(fx["y"]))
+    else:
+        assert_pinned(orc.rollout(weights("K4_F32"), cfg, g), torch.from_numpy(fx["rollout"]))
+
+
 def test_oracle_msgnn3_wet():
     fx = golden("fx_small3_msgnn3_wet")
     cfg = manifest()["weights_msgnn3_F32_seed666_cfg"]
