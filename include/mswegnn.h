@@ -229,6 +229,23 @@ int msw_set_group_graph(msw_plan* plans0, int enable);
 
 int msw_plan_get_stats(const msw_plan* plan, msw_plan_stats* stats);
 
+/* The plan's launch schedule as text: one line per launch of a rollout step (rollout = 1)
+ * or of msw_forward (rollout = 0), tab-separated key=value fields:
+ *   kind     encode | edge_hop | edge_mlp | hop | pool | epi | decode | exchange
+ *   variant  the kernel instantiation, a stable short name ("hop loop mid", "hop rows",
+ *            "edge_coop4 pool", "encode loop stream", "pool rows loop", ...)
+ *   nt scale prelu   F / 16, destination scale, compile-time PReLU path
+ *   grid waves       workgroups launched (before XCD padding), waves per workgroup
+ *   units per_wg     what the grid walks (edge tiles, row tiles, 64-row chunks or MLP chunks)
+ *                    and how many of them a workgroup takes per round
+ *   iters ragged     ceil(units / (grid * per_wg)): the most loop iterations any wave makes;
+ *                    1 if the last round is partly empty
+ *   lds              dynamic LDS bytes
+ * Produced by the same code that chooses what the launchers launch.  Writes at most `cap`
+ * bytes (NUL-terminated) to buf and the size needed, NUL included, to *needed; call with
+ * cap = 0 (buf may be NULL) to size the buffer. */
+int msw_plan_schedule(const msw_plan* plan, int32_t rollout, char* buf, int64_t cap, int64_t* needed);
+
 
 /* Re-launch one kernel of the step `iters` times on `stream` (benchmark / roofline hook;
  * call after a forward or rollout: it reuses the plan's workspaces and overwrites scratch).

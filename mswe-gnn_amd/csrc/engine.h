@@ -319,7 +319,29 @@ hipError_t launch_init_state(const InitArgs& a, hipStream_t st);
 hipError_t launch_copy_rows(const float* src, const int* srows, float* dst, const int* drows, int n, int width,
                             hipStream_t st);
 
+// What one launch runs: the kernel instantiation, its grid and workgroup, chosen from the
+// launch's arguments by pick_* (kernels/k_pick.h).  The launchers launch exactly this and
+// msw_plan_schedule prints it, so the description cannot drift from the launch.
+struct Pick {
+  const void* fn;   // the kernel (null with err = 0: nothing to launch)
+  char name[40];    // stable variant name: template family + the flags that choose the instantiation
+  int err;          // hipError_t of an argument combination no kernel exists for
+  int grid;         // workgroups, before XCD padding
+  int waves;        // waves per workgroup
+  int pack;         // 1: a one-round grid, packed onto few XCDs (xcd_grid)
+  size_t lds;       // dynamic LDS bytes
+  long units;       // what the grid walks: edge tiles, row tiles, 64-row chunks or MLP chunks
+  int per_wg;       // units one workgroup takes per round
+};
+
 // NT = F / 16 feature tiles (F = 16, 32, 64 -> NT = 1, 2, 4)
+template <int NT> Pick pick_encode(const EncodeArgs& a);
+template <int NT> Pick pick_edge_hop(const EdgeHopArgs& a);
+template <int NT> Pick pick_edge_mlp(const EdgeHopArgs& a);
+template <int NT> Pick pick_hop(const HopArgs& a);
+template <int NT> Pick pick_pool(const PoolArgs& a);
+template <int NT> Pick pick_epi(const EpiArgs& a);
+template <int NT> Pick pick_decode(const DecodeArgs& a);
 template <int NT> hipError_t prepare_kernels();
 // kind 0 encode, 1 edge_hop, 2 hop, 3 pool, 5 pool edge tiles, 6 row epilogue (and the
 // cooperative / split / row-layout variants, kernels_impl.h kernel_of)

@@ -18,7 +18,10 @@
 //    edge-MLP+hop-1, hops 2..K (the last with an epilogue: next projection / unpool
 //    projection / decoder + rollout update) -> pooling+projection / unpooling+projection.
 #pragma once
+#include <cstdio>
+#include <initializer_list>
 #include <type_traits>
+#include <utility>
 
 #include "engine.h"
 
@@ -58,6 +61,7 @@ constexpr int edge_eu() { return LOOP && NT <= 2 ? edge_waves<NT, LOOP, LST>() /
 #include "kernels/k_coop_encode.h"
 #include "kernels/k_hop.h"
 #include "kernels/k_pool_epi.h"
+#include "kernels/k_pick.h"
 #include "kernels/k_launch.h"
 
 }  // namespace msw

@@ -286,6 +286,12 @@ struct Knobs {
   int coop_waves = -1;      // MSW_COOP_WAVES      cooperative kernels while P x tiles <= this (-1 default)
   int epi_split_tiles = -1; // MSW_EPI_SPLIT_TILES row-epilogue threshold in edge tiles (-1 default)
   int trace_encode = 0;     // MSW_TRACE_ENCODE    diagnostic builds (-DMSW_TRACE): encoder marks only
+  // A test switch, not a tuning switch: every residency figure of this plan (resident_of) is
+  // clamped to n workgroups and the rules that go by absolute tile count (kHopLoopTiles,
+  // kRowHopMinTiles) are waived, so a small mesh gets, launch for launch, the schedule of a mesh
+  // too large for an n-workgroup chip -- every grid-stride kernel then makes several
+  // iterations per wave (tests/test_gpu_gridstride.py).  Off when unset or <= 0.
+  int grid_cap = 0;         // MSW_GRID_CAP        resident-grid cap in workgroups (tests)
 };
 inline Knobs knobs_from_env() {
   Knobs k;
@@ -296,7 +302,8 @@ inline Knobs knobs_from_env() {
       {"MSW_EH_LOOP", &k.eh_loop},
       {"MSW_HOP_SPLIT", &k.hop_split}, {"MSW_POOL_WIDE", &k.pool_wide}, {"MSW_TILE_PACK", &k.tile_pack},
       {"MSW_XCD_MAX", &k.xcd_max}, {"MSW_COOP_WAVES", &k.coop_waves},
-      {"MSW_EPI_SPLIT_TILES", &k.epi_split_tiles}, {"MSW_TRACE_ENCODE", &k.trace_encode}};
+      {"MSW_EPI_SPLIT_TILES", &k.epi_split_tiles}, {"MSW_TRACE_ENCODE", &k.trace_encode},
+      {"MSW_GRID_CAP", &k.grid_cap}};
   for (const auto& t : tab)
     if (const char* e = getenv(t.name)) *t.v = atoi(e);
   return k;
@@ -999,17 +1006,20 @@ int relocate(msw_plan* P, std::vector<Launch>& q, bool mlp_only = false) {
 
 // Grid cap of a grid-stride launch: the workgroups the chip holds at once, so that each
 // stages its weight region once (large meshes) and none waits for a second wave of blocks.
-int resident_of(int NT, int kind, int prelu, int last, size_t bytes, int loop) {
-  switch (NT) {
-    case 1: return resident_blocks<1>(kind, prelu, last, bytes, loop);
-    case 2: return resident_blocks<2>(kind, prelu, last, bytes, loop);
-    default: return resident_blocks<4>(kind, prelu, last, bytes, loop);
+// MSW_GRID_CAP=n (tests): at most n; 0 (the occupancy query failed) stays 0.
+int resident_of(const msw_plan* P, int kind, int prelu, int last, size_t bytes, int loop) {
+  int r;
+  switch (P->NT) {
+    case 1: r = resident_blocks<1>(kind, prelu, last, bytes, loop); break;
+    case 2: r = resident_blocks<2>(kind, prelu, last, bytes, loop); break;
+    default: r = resident_blocks<4>(kind, prelu, last, bytes, loop); break;
   }
+  return P->kn.grid_cap > 0 ? std::min(r, P->kn.grid_cap) : r;
 }
 template <class A>
 void caps(msw_plan* P, A& a, int kind, int prelu, int last, int floats) {
-  a.max_blocks = resident_of(P->NT, kind, prelu, last, (size_t)floats * 4, 1);
-  a.fit_blocks = resident_of(P->NT, kind, prelu, last, (size_t)floats * 4, 0);
+  a.max_blocks = resident_of(P, kind, prelu, last, (size_t)floats * 4, 1);
+  a.fit_blocks = resident_of(P, kind, prelu, last, (size_t)floats * 4, 0);
 }
 constexpr int kHopLoopTiles = 65536;
 // middle hops of scales with at least this many edge tiles run in the row layout
@@ -1024,7 +1034,7 @@ void set_grid_cap(msw_plan* P, Launch& L) {
   if (L.kind != L_HOP && L.kind != L_EDGE_HOP && L.kind != L_POOL && L.kind != L_EPI) L.common().xcd_max = 0;
   switch (L.kind) {
     case L_ENCODE: {
-      L.enc.max_blocks = resident_of(P->NT, 0, L.enc.c.prelu, 0, (size_t)L.enc.lds_floats * 4, 0);
+      L.enc.max_blocks = resident_of(P, 0, L.enc.c.prelu, 0, (size_t)L.enc.lds_floats * 4, 0);
       // F = 64: four waves per row tile while that leaves <= 4 waves per SIMD (k_encode_coop;
       // zenodo4_f64 +5.0 %; at F = 32 the halved chains are too short for the seven LDS
       // exchanges: -2.5 %; MSW_ENC_COOP=0/1 overrides)
@@ -1044,13 +1054,13 @@ void set_grid_cap(msw_plan* P, Launch& L) {
       // profiles/r04/ab_f64_lds_operands.txt; removed in round 6.)  Waves 4..7 start 2 x 2 k
       // cycles late (k_edge_mlp 22.0 -> 21.2 us, profiles/r05/ab_f64_mlp_stagger.txt).
       L.eh.stagger = kMlpStagger;
-      L.eh.max_blocks = resident_of(P->NT, 10, L.eh.c.prelu, 0, (size_t)L.eh.reg.len * 4, 1);
+      L.eh.max_blocks = resident_of(P, 10, L.eh.c.prelu, 0, (size_t)L.eh.reg.len * 4, 1);
       break;
     }
     case L_EDGE_HOP: {
       EdgeHopArgs& a = L.eh;
       caps(P, a, 1, a.c.prelu, a.last, a.reg.len);
-      a.fit_blocks = resident_of(P->NT, 1, a.c.prelu, a.last, (size_t)a.reg_nf * 4, 0);
+      a.fit_blocks = resident_of(P, 1, a.c.prelu, a.last, (size_t)a.reg_nf * 4, 0);
       // MSW_EH_LOOP=1: the grid-stride variant at any size (parity tests of the large-mesh path)
       if (P->kn.eh_loop && a.max_blocks > 0 && a.ntiles > kWaves) a.fit_blocks = 1;
       // two waves per tile (k_edge_coop) while the tiles leave most SIMDs idle: one tile
@@ -1061,7 +1071,7 @@ void set_grid_cap(msw_plan* P, Launch& L) {
       // halved MLP chain saves: measured +4.7 us on the finest unpooling of zenodo4)
       // (F = 32: two waves per tile; F = 64: four, one tile per workgroup)
       const int pw = P->NT == 2 ? 2 : P->NT == 4 ? 4 : 0;
-      const int coop_fit = pw ? resident_of(P->NT, 7, a.c.prelu, a.last, (size_t)a.reg_nf * 4, 0) : 0;
+      const int coop_fit = pw ? resident_of(P, 7, a.c.prelu, a.last, (size_t)a.reg_nf * 4, 0) : 0;
       a.coop = (pw && !loop && epi_ok && P->coop_waves > 0 && (long)pw * a.ntiles <= P->coop_waves &&
                 (pw * a.ntiles + kWaves - 1) / kWaves <= coop_fit) ? pw : 0;
       // F = 64 where four waves per tile do not fit one round: two, two tiles per workgroup
@@ -1076,10 +1086,10 @@ void set_grid_cap(msw_plan* P, Launch& L) {
       if (P->NT == 4 && !a.coop && !loop && epi_ok && P->coop_waves > 0 && 2L * a.ntiles <= P->coop_waves && c2) {
         const int need = (2 * a.ntiles + kWaves - 1) / kWaves;
         const int wd = P->kn.coop2_direct;
-        if (need <= resident_of(P->NT, 12, a.c.prelu, a.last, (size_t)a.reg_nf * 4, 0)) {
+        if (need <= resident_of(P, 12, a.c.prelu, a.last, (size_t)a.reg_nf * 4, 0)) {
           a.coop = 2;
           a.wdirect = wd == 2 && a.reg.len > 0;
-        } else if (wd != 0 && a.reg.len > 0 && need <= resident_of(P->NT, 12, a.c.prelu, a.last, 0, 0)) {
+        } else if (wd != 0 && a.reg.len > 0 && need <= resident_of(P, 12, a.c.prelu, a.last, 0, 0)) {
           // the staged MLP region (96 KB) holds one workgroup per CU: read it from its blob
           // copy instead, two workgroups per CU, and the grid fits one round (the finest
           // unpooling of zenodo4_f64: 652 tiles; MSW_COOP2_DIRECT=0 off)
@@ -1095,7 +1105,8 @@ void set_grid_cap(msw_plan* P, Launch& L) {
       // one tile per wave below kHopLoopTiles: the grid-stride variant measured 1.1-1.6 % slower on the batch of 8 and
       // dk15, equal on the 1M-node mesh whose finest hop alone it runs 3 % faster
       // (profiles/r01_v7/ab_edge_waves.txt)
-      if (L.hop.ntiles < kHopLoopTiles) L.hop.max_blocks = 0;
+      // (waived under MSW_GRID_CAP, whose point is the grid-stride variant on a small mesh)
+      if (L.hop.ntiles < kHopLoopTiles && P->kn.grid_cap <= 0) L.hop.max_blocks = 0;
       {  // F = 64: feature-split middle hops below the grid-stride size (k_hop_split;
          // zenodo4_f64 +4.6 %, F = 32 neutral; MSW_HOP_SPLIT=0/1 overrides the rule)
         bool sp = P->NT == 4 && L.hop.max_blocks == 0;
@@ -1110,7 +1121,7 @@ void set_grid_cap(msw_plan* P, Launch& L) {
         if (want && !h.last && (loop || row_hops_forced(P)) && h.rptr && h.redge) {
           h.rows = 1;
           h.split = 0;
-          h.max_blocks = resident_of(P->NT, 14, 0, 0, 0, 1);
+          h.max_blocks = resident_of(P, 14, 0, 0, 0, 1);
         }
       }
       {  // a last hop with an epilogue on few tiles: P = F / 16 waves per tile (k_hop_coop)
@@ -1119,7 +1130,7 @@ void set_grid_cap(msw_plan* P, Launch& L) {
         const int pw = P->NT >= 2 ? P->NT : 0;
         h.coop = 0;
         if (h.last && pw && !loop && P->coop_waves > 0 && (long)pw * h.ntiles <= P->coop_waves &&
-            (pw * h.ntiles + kWaves - 1) / kWaves <= resident_of(P->NT, 9, h.c.prelu, 1, (size_t)h.reg.len * 4, 0))
+            (pw * h.ntiles + kWaves - 1) / kWaves <= resident_of(P, 9, h.c.prelu, 1, (size_t)h.reg.len * 4, 0))
           h.coop = pw;
       }
       break;
@@ -1131,7 +1142,7 @@ void set_grid_cap(msw_plan* P, Launch& L) {
     default: {
       // edge tiles while they all fit on the chip at once (latency-bound launch), else rows
       PoolArgs& a = L.pool;
-      const int fe = resident_of(P->NT, 5, 0, 0, (size_t)a.reg.len * 4, 0);
+      const int fe = resident_of(P, 5, 0, 0, (size_t)a.reg.len * 4, 0);
       a.rows = !(fe > 0 && (a.etiles + kWaves - 1) / kWaves <= fe);
       a.ntiles = a.rows ? a.rtiles : a.etiles;
       caps(P, a, 3, 0, 0, a.reg.len);
@@ -1145,7 +1156,7 @@ void set_grid_cap(msw_plan* P, Launch& L) {
       // ab_pool_wide_f32.txt); MSW_POOL_WIDE=0: F / 16 waves; bit-identical either way
       const bool wide = P->kn.pool_wide != 0;
       if (wide && pw && a.coop == pw && a.np.h1t == 2 * pw) {
-        const int f8 = resident_of(P->NT, 13, 0, 0, (size_t)a.reg.len * 4, 0);
+        const int f8 = resident_of(P, 13, 0, 0, (size_t)a.reg.len * 4, 0);
         if (f8 > 0 && a.etiles <= f8) a.coop = 2 * pw;
       }
       break;
@@ -1177,6 +1188,21 @@ hipError_t launch_one(const Launch& L, hipStream_t st) {
     case L_EPI: return launch_epi<NT>(L.ep, st);
     case L_DECODE: return launch_decode<NT>(L.dec, st);
     default: return hipErrorInvalidValue;  // exchanges are run by run_schedule / the group driver
+  }
+}
+
+// What launch_one would launch (engine.h Pick): the launchers run these same pick_* functions.
+template <int NT>
+Pick pick_one(const Launch& L) {
+  switch (L.kind) {
+    case L_ENCODE: return pick_encode<NT>(L.enc);
+    case L_EDGE_HOP: return pick_edge_hop<NT>(L.eh);
+    case L_EDGE_MLP: return pick_edge_mlp<NT>(L.eh);
+    case L_HOP: return pick_hop<NT>(L.hop);
+    case L_POOL: return pick_pool<NT>(L.pool);
+    case L_EPI: return pick_epi<NT>(L.ep);
+    case L_DECODE: return pick_decode<NT>(L.dec);
+    default: return Pick{};
   }
 }
 
@@ -1281,7 +1307,7 @@ int build_graph_plan(msw_plan* P, const msw_graph_desc* g) {
   HostGraph H;
   std::string err;
   int rc = build_host_graph(g, P->S, kRowsPerBlock, P->kn.tile_pack != 0,
-                            row_hops_forced(P) ? 0 : kRowHopMinTiles, H, err);
+                            row_hops_forced(P) || P->kn.grid_cap > 0 ? 0 : kRowHopMinTiles, H, err);
   if (rc) return fail(rc, err);
   P->N = H.N;
   P->E = H.E;
@@ -1986,6 +2012,43 @@ int msw_set_trace(msw_plan* P, uint64_t* buf) {
     for (Launch& L : *q)
       L.common().trace = (!enc_only || L.kind == L_ENCODE) ? reinterpret_cast<unsigned long long*>(buf) : nullptr;
   P->drop_graphs();  // the captured steps hold the old arguments
+  return MSW_OK;
+}
+
+int msw_plan_schedule(const msw_plan* P, int32_t rollout, char* buf, int64_t cap, int64_t* needed) {
+  if (!P || !needed || (cap > 0 && !buf) || cap < 0) return fail(MSW_ERR_INVALID, "bad argument");
+  static const char* const kind_name[] = {"encode", "edge_hop", "hop", "pool", "exchange", "epi", "edge_mlp", "decode"};
+  std::string out;
+  for (const Launch& L : rollout ? P->sched_roll : P->sched_fwd) {
+    Launch M = L;  // Launch::common() is not const
+    Pick p{};
+    if (L.kind == L_EXCHANGE) {
+      snprintf(p.name, sizeof(p.name), "exchange");
+    } else {
+      switch (P->NT) {
+        case 1: p = pick_one<1>(L); break;
+        case 2: p = pick_one<2>(L); break;
+        default: p = pick_one<4>(L); break;
+      }
+    }
+    // iterations of the wave that makes the most: rounds of grid x per_wg units
+    const long round = (long)p.grid * p.per_wg;
+    const long iters = round > 0 ? (p.units + round - 1) / round : 0;
+    const int ragged = round > 0 && p.units % round != 0;
+    char line[320];
+    snprintf(line, sizeof(line),
+             "kind=%s\tvariant=%s\tnt=%d\tscale=%d\tprelu=%d\tgrid=%d\twaves=%d\tunits=%ld\tper_wg=%d\titers=%ld\t"
+             "ragged=%d\tlds=%zu\n",
+             kind_name[L.kind], p.name, P->NT, L.scale, M.common().prelu, p.grid, p.waves, p.units, p.per_wg, iters,
+             ragged, p.lds);
+    out += line;
+  }
+  *needed = (int64_t)out.size() + 1;
+  if (cap > 0) {
+    const size_t n = std::min(out.size(), (size_t)cap - 1);
+    memcpy(buf, out.data(), n);
+    buf[n] = 0;
+  }
   return MSW_OK;
 }
 

@@ -123,6 +123,7 @@ SYMBOLS = [
     ("msw_set_graph_capture", C.c_int, [C.c_void_p, C.c_int]),
     ("msw_set_group_graph", C.c_int, [C.c_void_p, C.c_int]),
     ("msw_plan_get_stats", C.c_int, [C.c_void_p, C.POINTER(MswPlanStats)]),
+    ("msw_plan_schedule", C.c_int, [C.c_void_p, C.c_int32, C.c_char_p, C.c_int64, c_int64_p]),
     ("msw_last_error", C.c_char_p, []),
     ("msw_abi_version", C.c_int, []),
     ("msw_struct_size", C.c_int64, [C.c_char_p]),

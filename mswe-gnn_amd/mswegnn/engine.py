@@ -307,6 +307,21 @@ class EnginePlan:
         out = {k: getattr(s, k) for k, _ in L.MswPlanStats._fields_}
         return out
 
+    def schedule(self, rollout=True):
+        """The launches of one rollout step (or of one forward), in order: a list of dicts
+        with `kind`, `variant` (the kernel instantiation, e.g. "hop loop mid"), `nt`, `scale`,
+        `prelu`, `grid`, `waves`, `units`, `per_wg`, `iters`, `ragged`, `lds`
+        (msw_plan_schedule: from the code that chooses what is launched)."""
+        need = C.c_int64(0)
+        L.check(L.lib().msw_plan_schedule(self._h, int(bool(rollout)), None, 0, C.byref(need)))
+        buf = C.create_string_buffer(need.value)
+        L.check(L.lib().msw_plan_schedule(self._h, int(bool(rollout)), buf, need.value, C.byref(need)))
+        out = []
+        for line in buf.value.decode().splitlines():
+            d = dict(f.split("=", 1) for f in line.split("\t"))
+            out.append({k: (v if k in ("kind", "variant") else int(v)) for k, v in d.items()})
+        return out
+
 
 # ------------------------------------------------------------------ cache
 _TOPOLOGY = {"GNN": ("edge_index", "edge_attr"),

@@ -6,7 +6,8 @@ hierarchical order.  The reference's real meshes are not (database/graph_creatio
 498-518, 922-927), and the engine has code only they reach: children beyond the inline pooling
 record and childless coarse rows with their "safe row" re-reads (in the fused pooling's slot
 records and in k_pool_edge -- the row-layout k_pool is chosen only when a level's pooling tiles
-do not fit resident, far above these sizes, and still runs on quadtree meshes only), fine rows
+do not fit resident, far above these sizes; tests/test_gpu_gridstride.py runs it on these meshes
+under MSW_GRID_CAP), fine rows
 without a parent in the fused unpooling, the dropped fused unpooling of a level with a two-parent node, in-degree 0/1/2
 rows inside edge tiles, pack_order on an irregular degree sequence, orphans in a decomposition,
 and the training kernels' pooling / intra-scale CSRs.  tests/test_irregular_mesh.py holds the

@@ -732,40 +732,76 @@ def test_wide_pool_matches_default(cuda, F, monkeypatch):
     assert per_step_rel(outs["1"][1], ref) <= REL_TOL
 
 
+def _switch_plans(cuda, monkeypatch, S, F, K, ck, knob, values, check):
+    """A 6-step wet-start rollout under `knob` = each of `values`, then under the last value
+    with MSW_GRID_CAP=2 (the forced kernel's loop then makes several iterations per wave);
+    check(schedule, value, capped) asserts which kernels each plan chose."""
+    from mswegnn.engine import EnginePlan
+    T = 6
+    g = wet_state(make_multiscale_mesh(**mesh_config("small" if S == 4 else "small3"), T=T), seed=4).to(cuda)
+    m = build_msgnn(S, F, K, state=weights(ck) if ck else None).to(cuda)
+    outs = []
+    for v, cap in [(v, None) for v in values] + [(values[-1], "2")]:
+        monkeypatch.setenv(knob, v)
+        if cap:
+            monkeypatch.setenv("MSW_GRID_CAP", cap)
+        else:
+            monkeypatch.delenv("MSW_GRID_CAP", raising=False)
+        plan = EnginePlan(m, g, cuda)
+        check(plan.schedule(), v, cap is not None)
+        outs.append(plan.rollout(g.x, g.BC, g.node_BC, g.type_BC, T).clone())
+        plan.close()
+    return outs
+
+
 @pytest.mark.parametrize("S,F,K,ck", [(4, 32, 4, "K4_F32"), (4, 16, 2, "K2_F16"), (4, 64, 4, None), (3, 32, 4, None)])
 def test_row_layout_hops_match_edge_tiles(cuda, monkeypatch, S, F, K, ck):
     """k_hop_rows (the row-layout middle hop of large meshes, forced on every scale here with
     MSW_HOP_ROWS=2) == the edge-tile k_hop bit for bit over a rollout (wet start: every
-    branch of the activity predicate)."""
-    from mswegnn.engine import EnginePlan
-    T = 6
-    g = wet_state(make_multiscale_mesh(**mesh_config("small" if S == 4 else "small3"), T=T), seed=4).to(cuda)
-    m = build_msgnn(S, F, K, state=weights(ck) if ck else None).to(cuda)
-    outs = []
-    for v in ("0", "2"):
-        monkeypatch.setenv("MSW_HOP_ROWS", v)
-        plan = EnginePlan(m, g, cuda)
-        outs.append(plan.rollout(g.x, g.BC, g.node_BC, g.type_BC, T).clone())
-        plan.close()
+    branch of the activity predicate) -- also on a grid capped to 2 workgroups, where a wave
+    walks several row tiles.  The plan's schedule says that every middle hop of every scale ran
+    in the row layout (K2_F16 has no middle hop: nothing to switch)."""
+    def check(sched, v, capped):
+        mid = [s for s in sched if s["kind"] == "hop" and s["variant"] != "hop coop" and " last" not in s["variant"]]
+        assert (len(mid) > 0) == (K > 2) and {s["scale"] for s in mid} == (set(range(S)) if K > 2 else set())
+        if v == "2":
+            assert all(s["variant"] == "hop rows" for s in mid), mid
+        else:
+            assert not any(s["variant"] == "hop rows" for s in sched), sched
+        if capped and mid:
+            assert all(s["grid"] <= 2 for s in mid) and max(s["iters"] for s in mid) >= 3, mid
+        elif mid:
+            assert all(s["iters"] == 1 for s in mid), mid
+    outs = _switch_plans(cuda, monkeypatch, S, F, K, ck, "MSW_HOP_ROWS", ("0", "2"), check)
     assert torch.equal(outs[0], outs[1])
+    assert torch.equal(outs[0], outs[2])
 
 
-@pytest.mark.parametrize("S,F,K,ck", [(4, 32, 4, "K4_F32"), (3, 32, 4, None), (4, 64, 4, None)])
+@pytest.mark.parametrize("S,F,K,ck", [(4, 32, 4, "K4_F32"), (3, 32, 4, None), (4, 64, 4, None), (4, 16, 2, "K2_F16")])
 def test_grid_stride_edge_hops_match_one_tile_per_wave(cuda, monkeypatch, S, F, K, ck):
     """The grid-stride fused edge MLP + hop of large meshes (staged weights once per
     workgroup, the next tile's lane record prefetched; forced at any size with MSW_EH_LOOP=1)
-    == the one-tile-per-wave kernels bit for bit over a wet-start rollout."""
-    from mswegnn.engine import EnginePlan
-    T = 6
-    g = wet_state(make_multiscale_mesh(**mesh_config("small" if S == 4 else "small3"), T=T), seed=4).to(cuda)
-    m = build_msgnn(S, F, K, state=weights(ck) if ck else None).to(cuda)
-    outs = []
-    for v in ("0", "1"):
-        monkeypatch.setenv("MSW_EH_LOOP", v)
-        plan = EnginePlan(m, g, cuda)
-        outs.append(plan.rollout(g.x, g.BC, g.node_BC, g.type_BC, T).clone())
-        plan.close()
+    == the one-tile-per-wave kernels bit for bit over a wet-start rollout -- also on a grid
+    capped to 2 workgroups, where a wave walks several tiles (uncapped, the chip holds more
+    workgroups than these meshes have rounds of tiles: one iteration).  The plan's schedule
+    says which launches the switch moved: every edge hop of more than four tiles, on every
+    scale, that has no pooling or unpooling fused in (those exist as cooperative kernels only)."""
+    def check(sched, v, capped):
+        eh = [s for s in sched if s["kind"] == "edge_hop"]
+        free = [s for s in eh if "pool" not in s["variant"] and s["units"] > 4]
+        loops = [s for s in eh if s["variant"].startswith("edge_hop loop")]
+        if v == "1":
+            assert free and loops == free, [(s["variant"], s["scale"], s["units"]) for s in eh]
+            assert 0 in {s["scale"] for s in loops}, loops
+        else:
+            assert not loops, loops
+        if capped:
+            assert all(s["grid"] <= 2 for s in loops) and max(s["iters"] for s in loops) >= 3, loops
+        else:
+            assert all(s["iters"] == 1 for s in eh), eh
+    outs = _switch_plans(cuda, monkeypatch, S, F, K, ck, "MSW_EH_LOOP", ("0", "1"), check)
     assert torch.equal(outs[0], outs[1])
+    assert torch.equal(outs[0], outs[2])
 
 
 def _built_variants():
