@@ -83,7 +83,9 @@ typedef struct {
  * 1 = GNN with type_GNN='SWEGNN' (models/gnn.py:13-152). */
 typedef struct {
   int32_t model_type;
-  int32_t hid_features;      /* F: 16, 32 or 64 supported (F=16 runs zero-padded to 32) */
+  int32_t hid_features;      /* F: 16, or 32..64.  16 / 32 / 64 run at their own width; 33..63 run
+                              * zero-padded to rows of 64 (msw_plan_stats.padded_features); every
+                              * tensor here keeps the model's own F-based shapes */
   int32_t num_scales;        /* S (GNN: 1) */
   int32_t previous_t;        /* p */
   int32_t num_node_features; /* static + 2p */
@@ -135,8 +137,8 @@ typedef struct {
   int64_t num_nodes;
   int64_t num_edges;
   int32_t num_scales;
-  int32_t hid_features;
-  int32_t padded_features;
+  int32_t hid_features;      /* the model's F */
+  int32_t padded_features;   /* row width of the plan's buffers and kernels: 16, 32 or 64 */
   int32_t kernels_per_step;  /* launches one forward enqueues */
   int64_t forward_calls;     /* forwards executed through the HIP path so far */
   int64_t rollout_steps;     /* rollout steps executed through the HIP path so far */

@@ -86,9 +86,15 @@ struct Common {
   int prelu;               // every MLP activation is PReLU (compile-time activation path)
   const float* zrow;       // kZeroRow zeros: the address of a load a flag switches off
   unsigned long long* trace;  // diagnostic builds (-DMSW_TRACE): per-phase timestamps of wave 0
-  int xcd_max;             // XCD packing of small grids: at most this many XCDs (0 = off)
+  // (two shorts in the place of one int: Common keeps its 64 bytes, so no launch's kernel
+  // arguments move; xcd_max is read on the host only, fl only by the ACT < 0 kernels)
+  short xcd_max;           // XCD packing of small grids: at most this many XCDs (0 = off)
+  short fl;                // the model's width: columns [fl, 16 NT) of every row are zero padding
+                           // (hid_features 33..63 at NT = 4; mask_pad, kernels/k_base.h)
   int xcd;                 // set by the launcher: this launch runs on XCDs 0 .. xcd-1 (0 = all)
 };
+
+static_assert(sizeof(Common) == 64, "Common: 64 bytes of every launch's kernel arguments");
 
 // Encoder.  Scale ranges start at multiples of 64 rows, so a workgroup has one scale.
 struct EncodeArgs {
@@ -334,7 +340,7 @@ struct Pick {
   int per_wg;       // units one workgroup takes per round
 };
 
-// NT = F / 16 feature tiles (F = 16, 32, 64 -> NT = 1, 2, 4)
+// NT = Fp / 16 feature tiles (row width Fp = 16, 32, 64 -> NT = 1, 2, 4; hid_features 33..63: Fp = 64)
 template <int NT> Pick pick_encode(const EncodeArgs& a);
 template <int NT> Pick pick_edge_hop(const EdgeHopArgs& a);
 template <int NT> Pick pick_edge_mlp(const EdgeHopArgs& a);

@@ -128,6 +128,22 @@ __device__ __forceinline__ void act_tiles(f32x4 (&v)[N], int act, float slope) {
   }
 }
 
+// Zero-padded widths (Common::fl < 16 NT): zero weights and biases keep the pad columns of every
+// row at f(0), which is 0 for every activation but the sigmoid (0.5).  Where something other
+// than a matrix product consumes an activated row -- the norm of s_ij, a stored x_s / x_d /
+// layer output -- the run-time-activation instantiations (ACT < 0) set columns >= fl to 0; the
+// compile-time PReLU kernels need nothing (and gain no instruction).  Lane group g holds
+// columns 16 t + 4 g + r of tile t.
+template <int ACT, int N>
+__device__ __forceinline__ void mask_pad(f32x4 (&v)[N], int fl, int g) {
+  if constexpr (ACT < 0) {
+#pragma unroll
+    for (int t = 0; t < N; ++t)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) v[t][r] = (16 * t + 4 * g + r < fl) ? v[t][r] : 0.f;
+  }
+}
+
 // acc[to] = sum_ti A[to][ti] in[ti]; A packed [TOUT][TIN].  Shapes are compile-time only:
 // a run-time bound here puts a branch after every MFMA (accumulator read-back + s_nop),
 // which measured ~130 cycles per 32-cycle MFMA.  The TOUT accumulators are independent
@@ -478,7 +494,10 @@ __device__ __forceinline__ void node_epilogue(f32x4 (&res)[NT], const Epilogue& 
                                               const EpiPre<NT>& pre, float* out, int n,
                                               bool valid, int lane, int g) {
   constexpr int F = 16 * NT, T2 = 2 * NT;
-  if (e.post_act) act_tiles<-1, NT>(res, e.post_act, e.post_slope);
+  if (e.post_act) {
+    act_tiles<-1, NT>(res, e.post_act, e.post_slope);
+    mask_pad<ACT, NT>(res, c.fl, g);
+  }
   if (out && valid) store_row<NT>(out + (size_t)n * F, res, NT, g);
   const bool np = e.np.a_u >= 0 || e.np.a_v >= 0 || e.np.a_o >= 0;
   if (np || e.uu_a >= 0) {

@@ -352,6 +352,7 @@ __device__ __forceinline__ void unpool_row(f32x4 (&res)[NT], const UnpoolIn<NT>&
 #pragma unroll
     for (int t = 0; t < NT; ++t) sv[t] = H[t];
   }
+  // (no mask_pad: unpooling is fused at NT = 2 only, plan.hip unpool_fusable -- never padded)
   if (d.normalize) normalize_s<NT>(sv);  // gnn.py:424-426
   // put_message with the destination's rows zero (own_zero), then its one-edge sum
   float rs = 0.f, rd = 0.f;
@@ -469,6 +470,7 @@ __global__ __launch_bounds__(64 * kWaves) void k_edge_coop(EdgeHopArgs a) {
 #pragma unroll
       for (int t = 0; t < NT; ++t) sv[t] = H[t];
     }
+    mask_pad<ACT, NT>(sv, a.c.fl, g);
     if (a.normalize) normalize_s<NT>(sv);  // gnn.py:424-426
     if (live && r == 0 && a.s) store_row<NT>(a.s + L.p * F, sv, NT, g);
     put_message<NT, FULL ? 1 : -1>(my, q.os, od, sv, L.ev, a.grad, a.upwind, g);
@@ -518,7 +520,10 @@ __global__ __launch_bounds__(64 * kWaves) void k_edge_coop(EdgeHopArgs a) {
     // ---- finish: store, or the epilogue (projections split over the ranks)
     if (LST && a.last) {
       const Epilogue& e = a.epi;
-      if (e.post_act) act_tiles<-1, NT>(res, e.post_act, e.post_slope);
+      if (e.post_act) {
+        act_tiles<-1, NT>(res, e.post_act, e.post_slope);
+        mask_pad<ACT, NT>(res, a.c.fl, g);
+      }
       if (live && r == 0 && a.out && L.nv) store_row<NT>(a.out + L.n * F, res, NT, g);
       if (e.np.h1t == T2)
         np_project_coop<NT, T2, P>(q.pre.xs, res, e.np, c.W, L.n, live && L.nv, r, lane, g);
@@ -674,6 +679,7 @@ __global__ __launch_bounds__(64 * kWaves) void k_edge_coop4(EdgeHopArgs a) {
 #pragma unroll
       for (int t = 0; t < NT; ++t) sv[t] = H[t];
     }
+    mask_pad<ACT, NT>(sv, a.c.fl, g);
     if (a.normalize) normalize_s<NT>(sv);  // gnn.py:424-426
     if (live && r == 0 && a.s) store_row<NT>(a.s + L.p * F, sv, NT, g);
     // every rank has read the slab's node rows before the first MLP exchange barrier: rank 0
@@ -716,7 +722,10 @@ __global__ __launch_bounds__(64 * kWaves) void k_edge_coop4(EdgeHopArgs a) {
     coop_exchange<NT, P>(rs, res, (a.rest.n & 1) ? &xbuf[1][0][0] : &xbuf[0][0][0], XW, r, j, g);
     if (LST && a.last) {
       const Epilogue& e = a.epi;
-      if (e.post_act) act_tiles<-1, NT>(res, e.post_act, e.post_slope);
+      if (e.post_act) {
+        act_tiles<-1, NT>(res, e.post_act, e.post_slope);
+        mask_pad<ACT, NT>(res, a.c.fl, g);
+      }
       if (live && r == 0 && a.out && L.nv) store_row<NT>(a.out + L.n * F, res, NT, g);
       if (e.np.h1t == T2)
         np_project_coop<NT, T2, P>(q.pre.xs, res, e.np, c.W, L.n, L.nv && live, r, lane, g);

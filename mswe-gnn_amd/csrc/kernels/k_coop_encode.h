@@ -207,6 +207,7 @@ __global__ __launch_bounds__(64 * WV) __attribute__((amdgpu_waves_per_eu(4))) vo
     for (int q = 0; q < 4; ++q) v[q] = (c.with_wl && 4 * g + q == nstat) ? wlv : raw[q];
     const f32x4 in[1] = {v};
     stat_mlp.run(in, xs, a.stat, Wl, lane, g, j, r, buf, xc, none);
+    mask_pad<ACT, NT>(xs, c.fl, g);
     if (valid && r == 0) store_row<NT>(a.xs + (size_t)n * F, xs, NT, g);
   }
   MSW_MARK(c, 5);
@@ -214,6 +215,7 @@ __global__ __launch_bounds__(64 * WV) __attribute__((amdgpu_waves_per_eu(4))) vo
     f32x4 xd[NT];
     const f32x4 in[1] = {f32x4{dyn[0], dyn[1], dyn[2], dyn[3]}};
     dyn_mlp.run(in, xd, a.dynm, Wl, lane, g, j, r, buf, xc, none);
+    mask_pad<ACT, NT>(xd, c.fl, g);
     if (valid && r == P - 1 && a.xd) store_row<NT>(a.xd + (size_t)n * F, xd, NT, g);
     MSW_MARK(c, 6);
     if (a.np0.h1t == T2)

@@ -239,6 +239,7 @@ __device__ __forceinline__ void edge_hop_core(const EdgeHopRows<NT>& r, const Ed
     for (int t = 0; t < NT; ++t) sv[t] = H[t];
   }
   MSW_MARK(c, 5);
+  mask_pad<ACT, NT>(sv, c.fl, g);
   if (a.normalize) normalize_s<NT>(sv);  // gnn.py:424-426
   if (a.s) store_row<NT>(a.s + L.p * F, sv, NT, g);  // padding slots too: never read
   put_message<NT, FULL ? 1 : -1>(my, r.os, od, sv, L.ev, a.grad, a.upwind, g);  // the slab row is free again
@@ -434,6 +435,7 @@ void k_edge_mlp(EdgeHopArgs a) {
 #pragma unroll
       for (int t = 0; t < NT; ++t) sv[t] = H[t];
     }
+    mask_pad<ACT, NT>(sv, a.c.fl, g);
     if (a.normalize) normalize_s<NT>(sv);  // gnn.py:424-426
     if (ev) store_row<NT>(a.s + (size_t)e.z * F, sv, NT, g);
   };

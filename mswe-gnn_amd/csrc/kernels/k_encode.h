@@ -101,6 +101,7 @@ __global__ __launch_bounds__(kBlock) void k_encode(EncodeArgs a) {
       for (int r = 0; r < 4; ++r) v[r] = (c.with_wl && 4 * g + r == nstat) ? wlv : raw[r];
       const f32x4 in[1] = {v};
       run_mlp<1, NT, NT, ACT>(in, xs, a.stat, Wl, lane, g);
+      mask_pad<ACT, NT>(xs, c.fl, g);
       if (valid) store_row<NT, ST>(a.xs + (size_t)n * F, xs, NT, g);
     }
     MSW_MARK(c, 5);
@@ -108,6 +109,7 @@ __global__ __launch_bounds__(kBlock) void k_encode(EncodeArgs a) {
       f32x4 xd[NT];
       const f32x4 in[1] = {f32x4{dyn[0], dyn[1], dyn[2], dyn[3]}};
       run_mlp<1, NT, NT, ACT>(in, xd, a.dynm, Wl, lane, g);
+      mask_pad<ACT, NT>(xd, c.fl, g);
       if (valid && a.xd) store_row<NT, ST>(a.xd + (size_t)n * F, xd, NT, g);
       MSW_MARK(c, 6);
       np_project<NT, ST>(xs, xd, a.np0, Wl, n, valid, lane, g);

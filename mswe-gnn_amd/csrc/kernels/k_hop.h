@@ -341,7 +341,10 @@ __device__ __forceinline__ void node_epilogue_coop(f32x4 (&res)[NT], const Epilo
                                                    int r, int lane, int g, int j, float* b0, float* b1, int xw) {
 #pragma clang fp contract(off)
   constexpr int F = 16 * NT, T2 = 2 * NT;
-  if (e.post_act) act_tiles<-1, NT>(res, e.post_act, e.post_slope);
+  if (e.post_act) {
+    act_tiles<-1, NT>(res, e.post_act, e.post_slope);
+    mask_pad<ACT, NT>(res, c.fl, g);
+  }
   if (out && valid && r == 0) store_row<NT>(out + (size_t)n * F, res, NT, g);
   if (e.np.a_u >= 0 || e.np.a_v >= 0 || e.np.a_o >= 0) {
     if (e.np.h1t == T2)

@@ -77,16 +77,35 @@ int pack_operand(Blob& B, const float* W, int in_dim, int tout, int tin, InMap i
   return off;
 }
 
+// Width embedding (hid_features 33..63 run zero-padded to Fp = 64): a dimension made of nb
+// blocks of F model features is stored as nb blocks of Fp, each block's features in its first
+// F columns.  Packed index k -> model index, or -1 for a pad column.  F == Fp: the identity
+// on [0, nb F).
+struct Embed {
+  int F, Fp;
+  int operator()(int k, int nb) const {
+    const int b = k / Fp, c = k % Fp;
+    return (b < nb && c < F) ? b * F + c : -1;
+  }
+};
+
 // Every layer gets a bias vector (zeros for bias=False): the kernels add it unconditionally.
-int pack_bias(Blob& B, const float* b, int out_dim, int tout) {
+// out_map as pack_operand's.
+template <class OutMap>
+int pack_bias(Blob& B, const float* b, int tout, OutMap out_map) {
   const int off = B.alloc((size_t)16 * tout);
   if (b)
-    for (int o = 0; o < out_dim; ++o) B.h[off + o] = b[o];
+    for (int q = 0; q < 16 * tout; ++q) {
+      const int o = out_map(q);
+      if (o >= 0) B.h[off + q] = b[o];
+    }
   return off;
 }
 
-// Pack a make_mlp stack (natural feature order in and out).
-int pack_mlp(Blob& B, const msw_mlp& m, MlpDev& d) {
+// Pack a make_mlp stack (natural feature order in and out).  Hidden widths are one feature
+// block (F, embedded into Fp); in_feat / out_feat: so are the stack's input / output
+// (otherwise raw columns: the encoders' inputs, the decoder's two outputs).
+int pack_mlp(Blob& B, const msw_mlp& m, MlpDev& d, Embed em, bool in_feat, bool out_feat) {
   if (m.n_layers < 1 || m.n_layers > kMaxLayers)
     return fail(MSW_ERR_UNSUPPORTED, "MLP depth must be 1.." + std::to_string(kMaxLayers));
   d.n = m.n_layers;
@@ -95,13 +114,15 @@ int pack_mlp(Blob& B, const msw_mlp& m, MlpDev& d) {
     if (!L.weight || L.in_features <= 0 || L.out_features <= 0)
       return fail(MSW_ERR_INVALID, "MLP layer without weight");
     if (L.act < 0 || L.act > 7) return fail(MSW_ERR_INVALID, "unknown activation code");
-    const int tin = tiles16(L.in_features), tout = tiles16(L.out_features);
     const int din = L.in_features, dout = L.out_features;
+    const bool fin = i > 0 || in_feat, fout = i + 1 < m.n_layers || out_feat;
+    const int tin = tiles16(fin ? em.Fp : din), tout = tiles16(fout ? em.Fp : dout);
+    auto inm = [&](int k) { return fin ? em(k, 1) : (k < din ? k : -1); };
+    auto outm = [&](int o) { return fout ? em(o, 1) : (o < dout ? o : -1); };
     d.l[i].tin = tin;
     d.l[i].tout = tout;
-    d.l[i].a_off = pack_operand(B, L.weight, din, tout, tin, [&](int k) { return k < din ? k : -1; },
-                                [&](int o) { return o < dout ? o : -1; });
-    d.l[i].b_off = pack_bias(B, L.bias, dout, tout);
+    d.l[i].a_off = pack_operand(B, L.weight, din, tout, tin, inm, outm);
+    d.l[i].b_off = pack_bias(B, L.bias, tout, outm);
     d.l[i].act = L.act;
     d.l[i].slope = L.act_param;
   }
@@ -311,7 +332,11 @@ inline Knobs knobs_from_env() {
 
 struct msw_plan {
   int device = 0;
-  int model_type = 0, F = 32, NT = 2, S = 1, p = 3, nnf = 8, dyn = 6, nstat_raw = 2;
+  // F: the model's hid_features -- only where the model's tensors are indexed (weight packing,
+  // the width checks, msw_debug_buffer).  Fp = 16 NT: the row width every buffer, stride,
+  // exchange row, LDS budget and kernel sees; Fp > F (33..63 -> 64) runs zero-padded.
+  int F = 32, Fp = 32;
+  int model_type = 0, NT = 2, S = 1, p = 3, nnf = 8, dyn = 6, nstat_raw = 2;
   int with_wl = 1, skip = 1;
   int N = 0, Npad = 0;
   int64_t E = 0;
@@ -447,7 +472,9 @@ int pupload(msw_plan* P, int2** p, const std::vector<I2>& v) {
 
 // SWEGNN layer -> packed Proc (gnn.py:352-445).
 int build_proc(msw_plan* P, const msw_swegnn& g, int scale, bool intra, Proc& pr) {
-  const int F = P->F, NT = P->NT;
+  // F: the model's width (indexes its tensors); Fp = 16 NT: the engine's row width
+  const int F = P->F, Fp = P->Fp, NT = P->NT;
+  const Embed em{F, Fp};
   pr.scale = scale;
   pr.K = g.K;
   pr.normalize = g.normalize;
@@ -465,24 +492,28 @@ int build_proc(msw_plan* P, const msw_swegnn& g, int scale, bool intra, Proc& pr
   for (int i = 1; i < m.n_layers; ++i)
     if (m.layer[i].in_features != 2 * F || m.layer[i].out_features != (i == m.n_layers - 1 ? F : 2 * F))
       return fail(MSW_ERR_UNSUPPORTED, "edge MLP layer widths must be 2F -> ... -> F");
-  pr.h1t = tiles16(H1);
+  const int hb = H1 / F;  // feature blocks of the hidden width (2, or 1 for one-layer MLPs)
+  pr.h1t = tiles16(hb * Fp);
   P->h1t_max = std::max(P->h1t_max, pr.h1t);
   const int din = L1.in_features;
   const float* W1 = L1.weight;
-  auto outm = [&](int o) { return o < H1 ? o : -1; };
+  auto outm = [&](int o) { return em(o, hb); };
   // cat(x_s[row], x_s[col], x_d[row], x_d[col], e_ij) (gnn.py:414-420): U takes the row
-  // (source) blocks, V the col (receiving) blocks; packed input = [x_s (F) | x_d (F)]
-  auto in_u = [&](int k) { return k < F ? k : (k < 2 * F ? 2 * F + (k - F) : -1); };
-  auto in_v = [&](int k) { return k < F ? F + k : (k < 2 * F ? 3 * F + (k - F) : -1); };
+  // (source) blocks, V the col (receiving) blocks; packed input = [x_s (Fp) | x_d (Fp)], W1's
+  // columns are the model's (blocks of F)
+  auto blk = [&](int k, int b_xs, int b_xd) {  // packed column -> W1 column (x_s / x_d block)
+    const int q = em(k, 2);
+    return q < 0 ? -1 : (q < F ? b_xs * F + q : b_xd * F + (q - F));
+  };
+  auto in_u = [&](int k) { return blk(k, 0, 2); };
+  auto in_v = [&](int k) { return blk(k, 1, 3); };
   pr.a_u = pack_operand(P->blob, W1, din, pr.h1t, 2 * NT, in_u, outm);
   pr.a_v = pack_operand(P->blob, W1, din, pr.h1t, 2 * NT, in_v, outm);
   if (intra)  // fine rows enter with x_d = 0: V from the x_s block alone
     pr.a_vu = pack_operand(P->blob, W1, din, pr.h1t, NT, [&](int k) { return k < F ? F + k : -1; }, outm);
   pr.act1 = L1.act;
   pr.slope1 = L1.act_param;
-  pr.b1_off = P->blob.alloc(16 * pr.h1t);
-  if (L1.bias)
-    for (int o = 0; o < H1; ++o) P->blob.h[pr.b1_off + o] = L1.bias[o];
+  pr.b1_off = pack_bias(P->blob, L1.bias, pr.h1t, outm);
   auto idF = [&](int q) { return q < F ? q : -1; };
   if (g.with_filter_matrix) {
     if (intra) return fail(MSW_ERR_UNSUPPORTED, "intra-scale SWEGNN with filter matrix");
@@ -498,13 +529,13 @@ int build_proc(msw_plan* P, const msw_swegnn& g, int scale, bool intra, Proc& pr
   pr.rest.n = m.n_layers - 1;
   for (int i = 1; i < m.n_layers; ++i) {
     const msw_linear& L = m.layer[i];
-    const int di = L.in_features, dout = L.out_features;
+    const int di = L.in_features, ob = L.out_features / F;  // 2F in; 2F or F out
     LayerDev& d = pr.rest.l[i - 1];
-    d.tin = tiles16(di);
-    d.tout = tiles16(dout);
-    d.a_off = pack_operand(P->blob, L.weight, di, d.tout, d.tin, [&](int k) { return k < di ? k : -1; },
-                           [&](int o) { return o < dout ? o : -1; });
-    d.b_off = pack_bias(P->blob, L.bias, dout, d.tout);
+    d.tin = tiles16(2 * Fp);
+    d.tout = tiles16(ob * Fp);
+    auto om = [&](int o) { return em(o, ob); };
+    d.a_off = pack_operand(P->blob, L.weight, di, d.tout, d.tin, [&](int k) { return em(k, 2); }, om);
+    d.b_off = pack_bias(P->blob, L.bias, d.tout, om);
     d.act = L.act;
     d.slope = L.act_param;
   }
@@ -528,7 +559,8 @@ NpDesc np_none() {
 Common common_of(msw_plan* P) {
   Common c{};
   c.W = P->dW; c.perm = P->perm_d; c.nnf = P->nnf; c.dyn = P->dyn; c.p = P->p; c.zrow = P->zrow_d;
-  c.xcd_max = P->xcd_max;
+  c.xcd_max = (short)P->xcd_max;
+  c.fl = (short)P->F;
   c.nstat_raw = P->nstat_raw; c.with_wl = P->with_wl; c.prelu = P->prelu;
   return c;
 }
@@ -576,7 +608,7 @@ void sched_proc(msw_plan* P, std::vector<Launch>& q, const Proc& pr, float* out,
                 const PoolFuse* pool = nullptr) {
   const ScaleCSR& g = P->sc[pr.scale];
   const Common c = common_of(P);
-  sched_exchange(P, q, pr.scale, {{pr.par ? B_U1 : B_U0, 16 * pr.h1t}, {pr.par ? B_O1 : B_O0, P->F}});
+  sched_exchange(P, q, pr.scale, {{pr.par ? B_U1 : B_U0, 16 * pr.h1t}, {pr.par ? B_O1 : B_O0, P->Fp}});
   Launch L1;
   L1.kind = L_EDGE_HOP;
   L1.scale = pr.scale;
@@ -620,7 +652,7 @@ void sched_proc(msw_plan* P, std::vector<Launch>& q, const Proc& pr, float* out,
   }
   const float* cur = P->T[0];
   for (int k = 2; k <= pr.K;) {
-    sched_exchange(P, q, pr.scale, {{cur == P->T[0] ? B_T0 : B_T1, P->F}});
+    sched_exchange(P, q, pr.scale, {{cur == P->T[0] ? B_T0 : B_T1, P->Fp}});
     // one launch per hop (hop chains -- several hops per launch with the halo recomputed --
     // measured 0.7-1.6 % slower under graph replay, profiles/r01_v7/ab_chains.txt; removed)
     const int m = 1;
@@ -1431,7 +1463,7 @@ int build_exchange(msw_plan* P, const msw_exchange_desc* d) {
     if ((rc = pupload(P, &Y.recv_rows, X[s].recv_rows)) || (rc = pupload(P, &Y.send_rows, X[s].send_rows))) return rc;
     most = std::max(most, (size_t)std::max(Y.nrecv, Y.nsend));
   }
-  const size_t floats = most * 2 * P->F;  // widest exchanged row: U (2F)
+  const size_t floats = most * 2 * P->Fp;  // widest exchanged row: U (2 Fp)
   if ((rc = palloc(P, &P->xsend, floats)) || (rc = palloc(P, &P->xrecv, floats))) return rc;
   return MSW_OK;
 }
@@ -1441,8 +1473,9 @@ int plan_create_impl(const msw_graph_desc* g, const msw_model_desc* m, int devic
   if (!g || !m || !out_plan) return fail(MSW_ERR_INVALID, "null argument");
   *out_plan = nullptr;
   if (m->model_type != 0 && m->model_type != 1) return fail(MSW_ERR_INVALID, "model_type must be 0 (MSGNN) or 1 (GNN)");
-  if (m->hid_features != 16 && m->hid_features != 32 && m->hid_features != 64)
-    return fail(MSW_ERR_UNSUPPORTED, "hid_features must be 16, 32 or 64");
+  // 16, 32, 64 run at their own width; 33..63 zero-padded to 64 (the F = 64 kernels)
+  if (m->hid_features != 16 && !(m->hid_features >= 32 && m->hid_features <= 64))
+    return fail(MSW_ERR_UNSUPPORTED, "hid_features must be 16 or 32..64 (33..63 run zero-padded to 64)");
   if (m->learned_pooling) return fail(MSW_ERR_UNSUPPORTED, "learned_pooling=True is not implemented");
   HIP_TRY(hipSetDevice(device));
   std::unique_ptr<msw_plan> P(new msw_plan());
@@ -1451,7 +1484,8 @@ int plan_create_impl(const msw_graph_desc* g, const msw_model_desc* m, int devic
   P->device = device;
   P->model_type = m->model_type;
   P->F = m->hid_features;
-  P->NT = P->F / 16;
+  P->Fp = P->F > 32 ? 64 : P->F;
+  P->NT = P->Fp / 16;
   P->S = m->model_type == 0 ? m->num_scales : 1;
   P->p = m->previous_t;
   P->nnf = m->num_node_features;
@@ -1472,7 +1506,7 @@ int plan_create_impl(const msw_graph_desc* g, const msw_model_desc* m, int devic
 
   P->kn = knobs_from_env();
   if (P->kn.epi_split_tiles >= 0) P->epi_split_tiles = P->kn.epi_split_tiles;
-  P->xcd_max = std::max(0, P->kn.xcd_max);
+  P->xcd_max = std::min(std::max(0, P->kn.xcd_max), kXcds);  // (more than eight means eight)
   // F = 64: four-wave cooperative kernels on every scale whose grid stays resident
   // (zenodo4_f64 +3.3 %, profiles/r02_v1/ab_coop_f64.txt); F = 32 keeps 1024 (no gain above)
   if (P->NT == 4) P->coop_waves = 4096;
@@ -1481,7 +1515,8 @@ int plan_create_impl(const msw_graph_desc* g, const msw_model_desc* m, int devic
   int rc = build_graph_plan(P.get(), g);
   if (rc) return rc;
   if (xch && (rc = build_exchange(P.get(), xch))) return rc;
-  const int F = P->F, Npad = P->Npad;
+  const int F = P->F, Fp = P->Fp, Npad = P->Npad;
+  const Embed em{F, Fp};
 
   // ---- weights
   auto chain_ok = [&](const msw_mlp& mm, int last_out) {
@@ -1495,9 +1530,9 @@ int plan_create_impl(const msw_graph_desc* g, const msw_model_desc* m, int devic
   if (!chain_ok(m->static_encoder, F) || !chain_ok(m->dynamic_encoder, F) || !chain_ok(m->decoder, 2) ||
       (m->edge_mlp && !chain_ok(m->edge_encoder, F)) || m->decoder.layer[0].in_features != F)
     return fail(MSW_ERR_UNSUPPORTED, "encoder/decoder hidden widths must equal hid_features");
-  if ((rc = pack_mlp(P->blob, m->static_encoder, P->stat))) return rc;
-  if ((rc = pack_mlp(P->blob, m->dynamic_encoder, P->dynm))) return rc;
-  if ((rc = pack_mlp(P->blob, m->decoder, P->dec))) return rc;
+  if ((rc = pack_mlp(P->blob, m->static_encoder, P->stat, em, false, true))) return rc;
+  if ((rc = pack_mlp(P->blob, m->dynamic_encoder, P->dynm, em, false, true))) return rc;
+  if ((rc = pack_mlp(P->blob, m->decoder, P->dec, em, true, false))) return rc;
   if (m->static_encoder.layer[0].in_features != P->nstat_raw + P->with_wl)
     return fail(MSW_ERR_INVALID, "static encoder input width");
   if (m->dynamic_encoder.layer[0].in_features != P->dyn) return fail(MSW_ERR_INVALID, "dynamic encoder input width");
@@ -1507,7 +1542,7 @@ int plan_create_impl(const msw_graph_desc* g, const msw_model_desc* m, int devic
   }
   const int ef_raw = g->num_edge_features;
   if (m->edge_mlp) {
-    if ((rc = pack_mlp(P->blob, m->edge_encoder, P->edge_enc))) return rc;
+    if ((rc = pack_mlp(P->blob, m->edge_encoder, P->edge_enc, em, false, true))) return rc;
     if (m->edge_encoder.layer[0].in_features != ef_raw) return fail(MSW_ERR_INVALID, "edge encoder input width");
     if (ef_raw > 16) return fail(MSW_ERR_UNSUPPORTED, "more than 16 raw edge features");
   } else if (ef_raw > F) {
@@ -1540,7 +1575,7 @@ int plan_create_impl(const msw_graph_desc* g, const msw_model_desc* m, int devic
   HIP_TRY(hipMemset(P->io_d, 0, sizeof(RolloutIO)));
   int Emax = 1;  // tile-padded edge slots of the largest scale
   for (auto& c : P->sc) Emax = std::max(Emax, c.ntiles * kRowsPerWave);
-  const size_t NF = (size_t)Npad * F;
+  const size_t NF = (size_t)Npad * Fp;
   const size_t NH = (size_t)Npad * 16 * P->h1t_max;
   float** bufs[] = {&P->xs, &P->xd0, &P->O[0], &P->O[1], &P->T[0], &P->T[1], &P->xdown, &P->xup, &P->xgnn};
   for (float** b : bufs) {
@@ -1552,7 +1587,7 @@ int plan_create_impl(const msw_graph_desc* g, const msw_model_desc* m, int devic
     if ((rc = palloc(P.get(), b, NH))) return rc;
     HIP_TRY(hipMemset(*b, 0, NH * sizeof(float)));
   }
-  if ((rc = palloc(P.get(), &P->s, (size_t)Emax * F))) return rc;
+  if ((rc = palloc(P.get(), &P->s, (size_t)Emax * Fp))) return rc;
   if ((rc = palloc(P.get(), &P->X, (size_t)Npad * P->nnf))) return rc;
   HIP_TRY(hipMemset(P->X, 0, (size_t)Npad * P->nnf * sizeof(float)));
   if (P->E > 0)
@@ -1609,27 +1644,27 @@ int plan_create_impl(const msw_graph_desc* g, const msw_model_desc* m, int devic
     const float* feat = ea_d;
     int feat_stride = ef_raw, feat_dim = ef_raw;
     if (m->edge_mlp) {
-      if ((rc = palloc(P.get(), &enc_d, (size_t)E * F))) return rc;
+      if ((rc = palloc(P.get(), &enc_d, (size_t)E * Fp))) return rc;
       RowMlpArgs ra{};
       ra.mode = 0;
       ra.in = ea_d; ra.in_stride = ef_raw; ra.in_dim = ef_raw; ra.R = (int)E; ra.m = P->edge_enc;
-      ra.W = P->dW; ra.out = enc_d; ra.out_stride = F; ra.out_tiles = P->NT;
+      ra.W = P->dW; ra.out = enc_d; ra.out_stride = Fp; ra.out_tiles = P->NT;
       P->edge_jobs.push_back(ra);
-      feat = enc_d; feat_stride = F; feat_dim = F;
+      feat = enc_d; feat_stride = Fp; feat_dim = F;  // rows of Fp, the first F the model's
     }
     for (size_t j = 0; j < P->procs.size(); ++j) {
       Proc& pr = P->procs[j];
       const msw_linear& L1 = m->processors[j].edge_mlp.layer[0];
-      const int H1 = L1.out_features;
+      const int hb = L1.out_features / F;  // hidden feature blocks, as build_proc
+      auto outm = [&](int o) { return em(o, hb); };
       Blob tb;  // Pe = W1[:, 4F:4F+ef] . feat + b1: one NT -> 2NT layer (zero padded)
       MlpDev md{};
       md.n = 1;
       md.l[0].tin = P->NT;
       md.l[0].tout = 2 * P->NT;
       md.l[0].a_off = pack_operand(tb, L1.weight, L1.in_features, 2 * P->NT, P->NT,
-                                   [&](int k) { return k < feat_dim ? 4 * F + k : -1; },
-                                   [&](int o) { return o < H1 ? o : -1; });
-      md.l[0].b_off = pack_bias(tb, L1.bias, H1, 2 * P->NT);
+                                   [&](int k) { return k < feat_dim ? 4 * F + k : -1; }, outm);
+      md.l[0].b_off = pack_bias(tb, L1.bias, 2 * P->NT, outm);
       md.l[0].act = 0;
       float* tw = nullptr;
       if ((rc = pupload(P.get(), &tw, tb.h))) return rc;
@@ -1994,11 +2029,12 @@ int msw_debug_buffer(msw_plan* P, const char* name, float* dst, void* stream) {
   if (!src) return fail(MSW_ERR_INVALID, std::string("unknown buffer ") + name);
   // debug only: synchronous host round trip into graph numbering
   HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-  std::vector<float> h((size_t)P->Npad * P->F), o((size_t)P->N * P->F);
+  // rows of Fp on the device, the model's F columns of each into the caller's [N][F]
+  std::vector<float> h((size_t)P->Npad * P->Fp), o((size_t)P->N * P->F);
   HIP_TRY(hipMemcpy(h.data(), src, h.size() * sizeof(float), hipMemcpyDeviceToHost));
   for (int i = 0; i < P->Npad; ++i)
     if (P->perm[i] >= 0)
-      std::copy(h.begin() + (size_t)i * P->F, h.begin() + (size_t)(i + 1) * P->F, o.begin() + (size_t)P->perm[i] * P->F);
+      std::copy(h.begin() + (size_t)i * P->Fp, h.begin() + (size_t)i * P->Fp + P->F, o.begin() + (size_t)P->perm[i] * P->F);
   HIP_TRY(hipMemcpy(dst, o.data(), o.size() * sizeof(float), hipMemcpyHostToDevice));
   return MSW_OK;
 }
@@ -2058,7 +2094,7 @@ int msw_plan_get_stats(const msw_plan* P, msw_plan_stats* s) {
   s->num_edges = P->E;
   s->num_scales = P->S;
   s->hid_features = P->F;
-  s->padded_features = P->F;
+  s->padded_features = P->Fp;
   s->kernels_per_step = P->kernels_per_step;
   s->forward_calls = P->forward_calls;
   s->rollout_steps = P->rollout_steps;

@@ -17,12 +17,15 @@ Execution paths of ``forward(graph)``:
 
 ``engine`` ('auto' | 'hip' | 'torch') on a model instance forces a path.  In 'auto' a
 configuration the engine does not implement (e.g. learned_pooling=True, hid_features other
-than 16/32/64, layer_norm MLPs, a node with more than 16 in-edges) and a training-mode model
-with dropout take the torch path; 'hip' raises for them instead.
+than 16 or 32..64, layer_norm MLPs, a node with more than 16 in-edges) and a training-mode model
+with dropout take the torch path; 'hip' raises for them instead.  When 'auto' takes the torch
+path because the engine refused the model or graph, the model warns once with the engine's
+reason and keeps it in ``engine_fallback_reason`` (None while the HIP path runs).
 
 Reference: GNN models/gnn.py:13-152, MSGNN :154-350, SWEGNN :352-450.
 """
 import contextvars
+import warnings
 import weakref
 from typing import Optional
 
@@ -173,6 +176,10 @@ class _EngineMixin:
     # 'auto': with autograd on a GPU, the encoders / decoder (and every SWEGNN layer, see
     # SWEGNN.train_engine) run on the HIP training kernels; 'torch': the modules themselves
     train_engine = "auto"
+    # engine='auto' only: why the engine refused this model / graph on the last call that asked
+    # it (the torch path ran instead), None when the HIP path ran
+    engine_fallback_reason = None
+    _fallback_warned = False
 
     def __init__(self, *args, **kwargs):
         # MSWEGNN_FUSED_ROLLOUT with training.train half-imported when models was: the callers
@@ -185,8 +192,19 @@ class _EngineMixin:
     def _engine_for(self, graph):
         """The cached plan for this graph, or None when engine='auto' and the engine does
         not implement this model / graph (the caller then takes the torch path)."""
-        from mswegnn.engine import plan_for
-        return plan_for(self, graph, unsupported_ok=getattr(self, "engine", "auto") == "auto")
+        from mswegnn.engine import plan_for, refusal_reason
+        plan = plan_for(self, graph, unsupported_ok=getattr(self, "engine", "auto") == "auto")
+        if plan is None:
+            reason = refusal_reason(self) or "unsupported model or graph"
+            if self.engine_fallback_reason != reason:
+                self.engine_fallback_reason = reason
+            if not self._fallback_warned:  # once per model
+                self._fallback_warned = True
+                warnings.warn(f"engine='auto': the HIP engine refused this model or graph ({reason}); "
+                              "running the torch path", RuntimeWarning, stacklevel=3)
+        elif self.engine_fallback_reason is not None:
+            self.engine_fallback_reason = None
+        return plan
 
     def _engine_forward(self, graph):
         """The forward on the HIP engine, or None (torch path).  The reference's rollout loop

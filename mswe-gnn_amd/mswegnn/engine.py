@@ -18,7 +18,7 @@ import torch.nn as nn
 
 from . import _lib as L
 
-__all__ = ["EnginePlan", "plan_for", "describe_model"]
+__all__ = ["EnginePlan", "plan_for", "describe_model", "refusal_reason"]
 
 _raw_stream = torch._C._cuda_getCurrentRawStream if hasattr(torch._C, "_cuda_getCurrentRawStream") \
     else (lambda i: torch.cuda.current_stream(i).cuda_stream)
@@ -409,6 +409,13 @@ def _weights_key(model):
 
 _plans = weakref.WeakKeyDictionary()
 CACHE_PLANS = 4  # plans kept per model (most recently used first)
+_refusals = weakref.WeakKeyDictionary()  # model -> why the engine last refused it (plan_for)
+
+
+def refusal_reason(model):
+    """The engine's own reason (msw_last_error text or the NotImplementedError raised while
+    describing the model) for the last ``plan_for(..., unsupported_ok=True)`` that gave None."""
+    return _refusals.get(model)
 
 
 def plan_for(model, graph, unsupported_ok=False):
@@ -449,6 +456,7 @@ def plan_for(model, graph, unsupported_ok=False):
         if not unsupported_ok or (isinstance(e, L.EngineError) and e.code != L.MSW_ERR_UNSUPPORTED):
             raise
         plan = None
+        _refusals[model] = str(e)
     entries.insert(0, (_GraphRef(model, graph), wk, plan))
     while len(entries) > CACHE_PLANS:
         old = entries.pop()[2]
