@@ -277,6 +277,50 @@ int msw_rollout_metrics(const float* pred, const float* real, int32_t T, const i
                         int32_t num_sims, const float* thresholds, int32_t n_thr, const float* area,
                         double* sums, uint64_t* counts, void* stream);
 
+/* On-device flood maps: a rollout reduced over time into per-cell maps, the sibling of
+ * msw_rollout_metrics.  The reference builds them on the host after every rollout:
+ * flood-arrival time WD_to_FAT (utils/miscellaneous.py:56-68, it counts wet steps), peak depth
+ * and discharge (utils/visualization.py:592-598), velocity and Froude number get_velocity /
+ * get_Froude (utils/miscellaneous.py:44-54). */
+#define MSW_MAX_MAP_THRESHOLDS 4
+typedef struct {            /* device pointers; NULL = this map is not produced            */
+  float*   h_max;           /* [nrows]                                                      */
+  int32_t* t_h_max;         /* [nrows] first global step attaining h_max                    */
+  float*   q_max;           /* [nrows] max |pred[:,1,:]|                                    */
+  int32_t* t_q_max;
+  float*   vel_max;         /* [nrows] max_t get_velocity(|q|, h, vel_eps)                  */
+  float*   froude_max;      /* [nrows] max_t get_Froude(vel, h)                             */
+  int32_t* wet_steps;       /* [n_thr][nrows] number of steps with h > thr                  */
+  int32_t* first_wet;       /* [n_thr][nrows] first / last global step with h > thr, or -1  */
+  int32_t* last_wet;
+} msw_flood_maps;
+
+/* Reduce steps t_begin .. t_begin + t_count - 1 of rows row0 .. row0 + nrows - 1 of pred (device
+ * [N][2][T], graph numbering, as msw_rollout writes it) into the maps (indexed by row - row0).
+ * The global step of column t is t_offset + (t - t_begin).  Per (row, step), with
+ * h = pred[n][0][t] and q = |pred[n][1][t]|:
+ *   vel = h > vel_eps ? q / h : 0          fr = h > 0 ? vel / sqrtf(9.81f * h) : 0
+ *   wet at threshold k iff h > thresholds[k]   (host float [n_thr], n_thr <= 4; strict)
+ * first = 1: the arrays are overwritten and need no initialisation.  first = 0: they hold the
+ * state of earlier calls and are continued -- a maximum moves only to a strictly larger value
+ * (the earliest step keeps a tie), first_wet is kept once set, last_wet and wet_steps advance --
+ * so a rollout fed piece by piece gives the maps of the whole.  The division and square root are
+ * skipped when vel_max and froude_max are both NULL, the threshold work when n_thr = 0.  Inputs
+ * are finite (the decoder's outputs are); NaN behaviour is unspecified.
+ * Stream-ordered, no host synchronisation, no allocation; needs no plan.  t_count = 0 or
+ * nrows = 0: no-op.  MSW_ERR_INVALID (before any HIP call): NULL pred or maps, NULL thresholds
+ * with n_thr > 0, n_thr outside 0..4, a window outside [0, T], negative row0 / nrows. */
+int msw_flood_maps_update(const float* pred, int32_t T, int32_t t_begin, int32_t t_count,
+                          int32_t t_offset, int64_t row0, int64_t nrows,
+                          const float* thresholds, int32_t n_thr, float vel_eps,
+                          int32_t first, const msw_flood_maps* maps, void* stream);
+/* The launch msw_flood_maps_update makes for that size (from the code the launcher itself uses):
+ * workgroups, rows a workgroup takes per round, and the rounds of its row loop, so that
+ * grid * rows_per_wg * iters >= nrows.  Windows longer than 1024 steps run as successive
+ * launches of at most 1024 steps; the numbers are those of each. */
+int msw_flood_maps_launch(int64_t nrows, int32_t t_count, int32_t* grid, int32_t* rows_per_wg,
+                          int32_t* iters);
+
 /* ---- Training: autograd through one SWEGNN processor ------------------------
  * Replaces the autograd of SWEGNN.forward (models/gnn.py:387-445) the reference trains through
  * in training_step (training/train.py:125-145).  Stateless: every buffer is device memory the

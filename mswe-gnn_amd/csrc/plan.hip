@@ -1432,6 +1432,7 @@ int64_t msw_struct_size(const char* name) {
   if (!strcmp(name, "msw_swegnn_grads")) return sizeof(msw_swegnn_grads);
   if (!strcmp(name, "msw_mlp_train_desc")) return sizeof(msw_mlp_train_desc);
   if (!strcmp(name, "msw_mlp_grads")) return sizeof(msw_mlp_grads);
+  if (!strcmp(name, "msw_flood_maps")) return sizeof(msw_flood_maps);
   return -1;
 }
 

@@ -111,6 +111,15 @@ class MswMlpGrads(C.Structure):
                 ("d_bias", C.c_void_p * MAX_MLP_LAYERS), ("d_slope", C.c_void_p * MAX_MLP_LAYERS)]
 
 
+MAX_MAP_THRESHOLDS = 4
+
+
+class MswFloodMaps(C.Structure):
+    _fields_ = [("h_max", C.c_void_p), ("t_h_max", C.c_void_p), ("q_max", C.c_void_p),
+                ("t_q_max", C.c_void_p), ("vel_max", C.c_void_p), ("froude_max", C.c_void_p),
+                ("wet_steps", C.c_void_p), ("first_wet", C.c_void_p), ("last_wet", C.c_void_p)]
+
+
 # (name, restype, argtypes) of every entry point declared in include/mswegnn.h
 SYMBOLS = [
     ("msw_plan_create", C.c_int, [C.POINTER(MswGraphDesc), C.POINTER(MswModelDesc), C.c_int,
@@ -133,6 +142,10 @@ SYMBOLS = [
     ("msw_rollout_metrics", C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, c_int64_p, C.c_int32,
                                       c_float_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p]),
+    ("msw_flood_maps_update", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64,
+                                        C.c_int64, c_float_p, C.c_int32, C.c_float, C.c_int32,
+                                        C.POINTER(MswFloodMaps), C.c_void_p]),
+    ("msw_flood_maps_launch", C.c_int, [C.c_int64, C.c_int32, c_int32_p, c_int32_p, c_int32_p]),
     ("msw_plan_create_part", C.c_int, [C.POINTER(MswGraphDesc), C.POINTER(MswModelDesc), C.c_int,
                                        C.POINTER(MswExchangeDesc), C.c_int32, C.POINTER(C.c_void_p)]),
     ("msw_comm_unique_id", C.c_int, [C.c_char_p]),
@@ -161,7 +174,8 @@ STRUCTS = {"msw_linear": MswLinear, "msw_mlp": MswMlp, "msw_swegnn": MswSwegnn,
            "msw_model_desc": MswModelDesc, "msw_graph_desc": MswGraphDesc,
            "msw_plan_stats": MswPlanStats, "msw_exchange_desc": MswExchangeDesc,
            "msw_swegnn_train_desc": MswSwegnnTrainDesc, "msw_swegnn_grads": MswSwegnnGrads,
-           "msw_mlp_train_desc": MswMlpTrainDesc, "msw_mlp_grads": MswMlpGrads}
+           "msw_mlp_train_desc": MswMlpTrainDesc, "msw_mlp_grads": MswMlpGrads,
+           "msw_flood_maps": MswFloodMaps}
 
 _lib = None
 
