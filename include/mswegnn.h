@@ -321,6 +321,56 @@ int msw_flood_maps_update(const float* pred, int32_t T, int32_t t_begin, int32_t
 int msw_flood_maps_launch(int64_t nrows, int32_t t_count, int32_t* grid, int32_t* rows_per_wg,
                           int32_t* iters);
 
+/* On-device zone series: a rollout reduced over space into per-(zone, step) series, the spatial
+ * sibling of the flood maps.  A zone is a list of graph rows (a district, a river reach, one
+ * simulation of a batch); a gauge is a zone of one row.  The reference has no counterpart beyond
+ * the stored volume inside its mass-conservation metric (training/loss.py:120-169).
+ *
+ * A zone set is built once per mesh: zone z = rows zone_rows[zone_ptr[z] .. zone_ptr[z+1]) (HOST
+ * arrays, zone_ptr [num_zones + 1] starting at 0; graph row ids in [0, num_rows), in any order; a
+ * row may appear in several zones or twice in one -- it then counts twice; empty zones allowed).
+ * The handle holds device copies of the lists, the launch's work list and the scratch of the
+ * partial sums, so updates that share a handle must be ordered on one stream.  device = -1 makes
+ * a host-only handle that answers msw_zone_series_launch and cannot be updated.
+ * MSW_ERR_INVALID, before any HIP call and with nothing allocated: a row id outside
+ * [0, num_rows), a zone_ptr that does not start at 0 or is not monotone, NULLs. */
+typedef struct msw_zones msw_zones;
+int msw_zones_create(const int64_t* zone_ptr, const int32_t* zone_rows, int64_t num_zones,
+                     int64_t num_rows, int device, msw_zones** out);
+int msw_zones_destroy(msw_zones* zones);
+
+typedef struct {          /* device pointers, NULL = not produced; leading stride T_out            */
+  double*  volume;        /* [Z][T_out]        sum (double)a * (double)h over the zone's rows       */
+  double*  wet_area;      /* [n_thr][Z][T_out] sum (double)a over rows with h > thr_k (strict)      */
+  int32_t* wet_cells;     /* [n_thr][Z][T_out] number of such rows                                  */
+  float*   h_max;         /* [Z][T_out]        max h   (0 for an empty zone)                        */
+  float*   q_max;         /* [Z][T_out]        max |pred[:,1,:]| (0 for an empty zone)              */
+} msw_zone_series;
+
+/* Steps t_begin .. t_begin + t_count - 1 of pred (device [N][2][T], graph numbering, N = num_rows
+ * of the zone set) -> columns t_out0 .. t_out0 + t_count - 1 of the outputs; columns outside the
+ * window are not touched, the window's are overwritten (no initialisation needed).
+ * a = area[row] (device float [N]) or 1.0f when area is NULL.  thresholds: host float [n_thr],
+ * n_thr <= MSW_MAX_MAP_THRESHOLDS.
+ * wet_cells, h_max and q_max are exact.  volume and wet_area are fp64 sums of terms that are exact
+ * in fp64, added in an order that the row list alone fixes: chunks of 256 consecutive list entries
+ * summed in list order from 0, then -- for a zone of several chunks -- the chunk sums in chunk
+ * order.  No atomics: the sums are the same bit for bit from call to call and however a rollout is
+ * cut into windows or pieces.  Inputs are finite; NaN behaviour is unspecified.
+ * Stream-ordered, no host synchronisation, no allocation.  t_count = 0 or no zones: no-op.
+ * MSW_ERR_INVALID (before any HIP call): NULL zones, pred or out, NULL thresholds with n_thr > 0,
+ * n_thr outside 0..4, a window outside [0, T], t_out0 < 0 or t_out0 + t_count > T_out. */
+int msw_zone_series_update(const msw_zones* zones, const float* pred, int32_t T, int32_t t_begin,
+                           int32_t t_count, const float* area, const float* thresholds, int32_t n_thr,
+                           int32_t T_out, int32_t t_out0, const msw_zone_series* out, void* stream);
+/* The launch msw_zone_series_update makes for that window (from the code the launcher itself
+ * uses).  A unit is one chunk of a zone's list x one tile of 64 steps: workgroups, units a
+ * workgroup takes per round of its loop (1: a workgroup is one wave) and the rounds, so that
+ * grid * units_per_wg * iters >= units.  Windows longer than the handle's scratch holds (at most
+ * 1024 steps) run as successive launches; the numbers are those of the first. */
+int msw_zone_series_launch(const msw_zones* zones, int32_t t_count, int32_t* grid,
+                           int32_t* units_per_wg, int32_t* iters);
+
 /* ---- Training: autograd through one SWEGNN processor ------------------------
  * Replaces the autograd of SWEGNN.forward (models/gnn.py:387-445) the reference trains through
  * in training_step (training/train.py:125-145).  Stateless: every buffer is device memory the

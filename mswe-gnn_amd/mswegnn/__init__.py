@@ -5,8 +5,8 @@ replaces the reference's ``models`` namespace package; the reference's own ``tra
 ``utils`` stay in charge of everything else.  This package holds the C-ABI
 binding (``_lib``), plans (``engine``), the rollout-path operators and the fused
 ``rollout_test`` (``rollout``), batching (``batch``), partitioning (``partition``),
-on-device metrics (``metrics``), on-device flood maps and chunked rollouts (``floodmaps``) and
-the synthetic meshes (``mesh``).
+on-device metrics (``metrics``), on-device flood maps and chunked rollouts (``floodmaps``), on-device
+zone series (``series``) and the synthetic meshes (``mesh``).
 """
 import os
 import sys

@@ -120,6 +120,11 @@ class MswFloodMaps(C.Structure):
                 ("wet_steps", C.c_void_p), ("first_wet", C.c_void_p), ("last_wet", C.c_void_p)]
 
 
+class MswZoneSeries(C.Structure):
+    _fields_ = [("volume", C.c_void_p), ("wet_area", C.c_void_p), ("wet_cells", C.c_void_p),
+                ("h_max", C.c_void_p), ("q_max", C.c_void_p)]
+
+
 # (name, restype, argtypes) of every entry point declared in include/mswegnn.h
 SYMBOLS = [
     ("msw_plan_create", C.c_int, [C.POINTER(MswGraphDesc), C.POINTER(MswModelDesc), C.c_int,
@@ -146,6 +151,12 @@ SYMBOLS = [
                                         C.c_int64, c_float_p, C.c_int32, C.c_float, C.c_int32,
                                         C.POINTER(MswFloodMaps), C.c_void_p]),
     ("msw_flood_maps_launch", C.c_int, [C.c_int64, C.c_int32, c_int32_p, c_int32_p, c_int32_p]),
+    ("msw_zones_create", C.c_int, [c_int64_p, c_int32_p, C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_void_p)]),
+    ("msw_zones_destroy", C.c_int, [C.c_void_p]),
+    ("msw_zone_series_update", C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                         c_float_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(MswZoneSeries),
+                                         C.c_void_p]),
+    ("msw_zone_series_launch", C.c_int, [C.c_void_p, C.c_int32, c_int32_p, c_int32_p, c_int32_p]),
     ("msw_plan_create_part", C.c_int, [C.POINTER(MswGraphDesc), C.POINTER(MswModelDesc), C.c_int,
                                        C.POINTER(MswExchangeDesc), C.c_int32, C.POINTER(C.c_void_p)]),
     ("msw_comm_unique_id", C.c_int, [C.c_char_p]),
@@ -175,7 +186,7 @@ STRUCTS = {"msw_linear": MswLinear, "msw_mlp": MswMlp, "msw_swegnn": MswSwegnn,
            "msw_plan_stats": MswPlanStats, "msw_exchange_desc": MswExchangeDesc,
            "msw_swegnn_train_desc": MswSwegnnTrainDesc, "msw_swegnn_grads": MswSwegnnGrads,
            "msw_mlp_train_desc": MswMlpTrainDesc, "msw_mlp_grads": MswMlpGrads,
-           "msw_flood_maps": MswFloodMaps}
+           "msw_flood_maps": MswFloodMaps, "msw_zone_series": MswZoneSeries}
 
 _lib = None
 
