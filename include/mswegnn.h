@@ -87,7 +87,7 @@ typedef struct {
                               * zero-padded to rows of 64 (msw_plan_stats.padded_features); every
                               * tensor here keeps the model's own F-based shapes */
   int32_t num_scales;        /* S (GNN: 1) */
-  int32_t previous_t;        /* p */
+  int32_t previous_t;        /* p, 1..8 (else MSW_ERR_UNSUPPORTED) */
   int32_t num_node_features; /* static + 2p */
   int32_t with_WL;           /* append DEM + h_t to the static input (gnn.py:288-291) */
   int32_t skip_connections;  /* MSGNN x_down skips (gnn.py:330-331) */

@@ -1498,6 +1498,8 @@ int plan_create_impl(const msw_graph_desc* g, const msw_model_desc* m, int devic
   P->gnn_act = m->gnn_act;
   P->gnn_slope = m->gnn_act_param;
   if (P->S < 1) return fail(MSW_ERR_INVALID, "num_scales < 1");
+  // the kernels write the newest state pair at columns dyn - 2 and dyn - 1 of a row
+  if (P->p < 1) return fail(MSW_ERR_UNSUPPORTED, "previous_t must be 1..8");
   if (P->nstat_raw < 1 || P->nstat_raw + P->with_wl > 16 || P->dyn > 16)
     return fail(MSW_ERR_UNSUPPORTED, "node feature layout (static / dynamic widths)");
   if (m->model_type == 0 && m->num_processors != 2 * P->S - 1)

@@ -7,6 +7,9 @@ of random sizes, dry or wet, and compares a 3-step rollout (rollout_test semanti
 the oracle at the fp32 bar (per step 1e-4 relative; a mask-threshold flip of the fp32
 reference itself is judged against fp64, conftest.assert_rollout_parity).  The shipped
 configurations are covered elsewhere; this looks for combinations no fixed test names.
+With the seeded init a rollout barely sees the processors (every SWEGNN output x 1.1 moves seed
+4's by 1.7e-4), so each case also compares one forward's intermediates with the oracle's: x_s,
+x_d (finest rows), x_down and x_up (msw_debug_buffer; the GNN has the first two only).
 FUZZ_SEEDS="a:b" widens the seed range (default 0:16) for a longer sweep on the GPU box.
 """
 import os
@@ -15,9 +18,11 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import assert_rollout_parity, build_gnn, build_msgnn, state_dict_of
+from conftest import REL_TOL, assert_rollout_parity, build_gnn, build_msgnn, rel_err, state_dict_of
+import layout_cases as lc
 import msgnn_torch as orc
 from mswegnn.batch import collate
+from mswegnn.engine import EnginePlan
 from mswegnn.mesh import make_multiscale_mesh, make_single_scale_mesh, wet_state
 from mswegnn.rollout import adapt_batch_training, rollout_test
 
@@ -89,3 +94,17 @@ def test_random_configuration_vs_oracle(cuda, seed):
     r = rollout_test(m, b.to(cuda)).cpu()
     assert r.shape == ref.shape
     assert_rollout_parity(r, ref, P, cfg, ref_graph, T, label=f"fuzz {seed} {c}")
+    # one forward's intermediates: the encoders' outputs and every processor's on its scale
+    want = lc.observe(P, cfg, ref_graph, T, rollout=False)
+    gd = ref_graph.to(cuda)
+    plan = EnginePlan(m, gd, cuda)
+    try:
+        plan.forward(gd.x)
+        names = ("x_s", "x_d") if c["S"] == 1 else ("x_s", "x_d", "x_down", "x_up")
+        got = lc.select(cfg, {k: plan.debug_buffer(k, c["F"]).cpu() for k in names}, ref_graph)
+    finally:
+        plan.close()
+    errs = {k: rel_err(v, want[k]) for k, v in got.items()}
+    print(f"fuzz {seed}: forward intermediates rel " + ", ".join(f"{k} {e:.2e}" for k, e in errs.items()))
+    assert all(v.shape == want[k].shape for k, v in got.items())
+    assert all(e <= REL_TOL for e in errs.values()), errs
