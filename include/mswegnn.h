@@ -272,10 +272,21 @@ int msw_bench_kernel(msw_plan* plan, int32_t kernel, int32_t scale, int32_t iter
  *          over rows with dh != 0 or dv != 0 (mask_on_water), that row count, and the
  *          stored volume sum(area * h_pred) (0 when area is NULL);
  *   counts uint64 [num_sims][T][n_thr][4]: TP, TN, FP, FN of h_pred > thr vs h_real > thr.
- * Stream-ordered, no host synchronisation; needs no plan. */
+ * A simulation with an empty range gets zero sums and its counts are left as they are.
+ * Stream-ordered, no host synchronisation; needs no plan.  T = 0: no-op.  MSW_ERR_INVALID
+ * (before any HIP call): NULL pred, real, fine_ranges or sums, NULL thresholds or counts with
+ * n_thr > 0, n_thr outside 0..4, negative T or num_sims, a range with end < start, a negative
+ * start, or an end past the kernel's int32 row indices. */
 int msw_rollout_metrics(const float* pred, const float* real, int32_t T, const int64_t* fine_ranges,
                         int32_t num_sims, const float* thresholds, int32_t n_thr, const float* area,
                         double* sums, uint64_t* counts, void* stream);
+/* The launch msw_rollout_metrics makes for one simulation of nrows finest rows over T steps (from
+ * the code the launcher itself uses): workgroups along the rows (at most 512), chunks of 32 steps
+ * (the grid is grid x time_chunks), rows a workgroup takes per round (256) and the rounds of its
+ * grid-stride row loop, so that grid * rows_per_wg * iters >= nrows.  nrows = 0 or T = 0: grid,
+ * time_chunks and iters are 0.  MSW_ERR_INVALID: negative nrows or T, a NULL output.  Host only. */
+int msw_rollout_metrics_launch(int64_t nrows, int32_t T, int32_t* grid, int32_t* time_chunks,
+                               int32_t* rows_per_wg, int32_t* iters);
 
 /* On-device flood maps: a rollout reduced over time into per-cell maps, the sibling of
  * msw_rollout_metrics.  The reference builds them on the host after every rollout:

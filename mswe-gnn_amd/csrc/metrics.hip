@@ -84,7 +84,7 @@ __global__ __launch_bounds__(kThreads) void k_metrics(MetricArgs a) {
       acc[6] += wet ? qh : 0.0;
       acc[7] += wet ? qv : 0.0;
       acc[8] += wet ? 1.0 : 0.0;
-      acc[9] += ar * (double)ph;
+      acc[9] += a.area ? ar * (double)ph : 0.0;  // 0 without area, also where ph is NaN or inf
       for (int k = 0; k < a.nthr; ++k) {
         const bool p = ph > a.thr[k], r = rh > a.thr[k];
         const unsigned long long tp = __popcll(__ballot(valid && p && r));
@@ -127,7 +127,35 @@ __global__ __launch_bounds__(kThreads) void k_metrics_reduce(const double* __res
   sums[i] = v;
 }
 
+struct Launch {
+  int grid, time_chunks, iters;
+};
+
+// The launch of one simulation of nrows finest rows over T steps: msw_rollout_metrics_launch
+// reports it, the launcher uses it.
+Launch pick_launch(int64_t nrows, int T) {
+  Launch l{0, 0, 0};
+  if (nrows <= 0 || T <= 0) return l;
+  const int64_t blocks = (nrows + kThreads - 1) / kThreads;
+  l.grid = (int)std::min<int64_t>(kMaxParts, blocks);
+  l.time_chunks = (T + kTChunk - 1) / kTChunk;
+  l.iters = (int)((blocks + l.grid - 1) / l.grid);
+  return l;
+}
+
 }  // namespace
+
+extern "C" int msw_rollout_metrics_launch(int64_t nrows, int32_t T, int32_t* grid, int32_t* time_chunks,
+                                          int32_t* rows_per_wg, int32_t* iters) {
+  if (!grid || !time_chunks || !rows_per_wg || !iters) return msw::set_error(MSW_ERR_INVALID, "null argument");
+  if (nrows < 0 || T < 0) return msw::set_error(MSW_ERR_INVALID, "nrows or T negative");
+  const Launch l = pick_launch(nrows, T);
+  *grid = l.grid;
+  *time_chunks = l.time_chunks;
+  *rows_per_wg = kThreads;
+  *iters = l.iters;
+  return MSW_OK;
+}
 
 extern "C" int msw_rollout_metrics(const float* pred, const float* real, int32_t T,
                                    const int64_t* fine_ranges, int32_t num_sims,
@@ -146,7 +174,10 @@ extern "C" int msw_rollout_metrics(const float* pred, const float* real, int32_t
   for (int g = 0; g < num_sims; ++g) {
     const long nr = fine_ranges[2 * g + 1] - fine_ranges[2 * g];
     if (nr < 0) return msw::set_error(MSW_ERR_INVALID, "fine range end < start");
-    nb_max = std::max(nb_max, (int)std::min<long>(kMaxParts, (nr + kThreads - 1) / kThreads));
+    // the kernel's row indices are int, and its loop runs one grid round past nrows
+    if (fine_ranges[2 * g] < 0 || fine_ranges[2 * g + 1] > INT32_MAX - kMaxParts * kThreads)
+      return msw::set_error(MSW_ERR_INVALID, "fine range negative or past the int32 row limit");
+    nb_max = std::max(nb_max, pick_launch(nr, T).grid);
   }
   double* part = nullptr;
   if (nb_max > 0) {
@@ -170,11 +201,11 @@ extern "C" int msw_rollout_metrics(const float* pred, const float* real, int32_t
       e = hipMemsetAsync(out, 0, (size_t)count * sizeof(double), st);
       continue;
     }
-    const int nb = (int)std::min<long>(kMaxParts, ((long)a.nrows + kThreads - 1) / kThreads);
+    const Launch l = pick_launch(a.nrows, T);
     a.part = part;
-    hipLaunchKernelGGL(k_metrics, dim3(nb, (T + kTChunk - 1) / kTChunk), dim3(kThreads), 0, st, a);
+    hipLaunchKernelGGL(k_metrics, dim3(l.grid, l.time_chunks), dim3(kThreads), 0, st, a);
     hipLaunchKernelGGL(k_metrics_reduce, dim3((unsigned)((count + kThreads - 1) / kThreads)), dim3(kThreads), 0, st,
-                       (const double*)part, nb, count, out);
+                       (const double*)part, l.grid, count, out);
     e = hipGetLastError();
   }
   const hipError_t f = part ? hipFreeAsync(part, st) : hipSuccess;

@@ -147,6 +147,7 @@ SYMBOLS = [
     ("msw_rollout_metrics", C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, c_int64_p, C.c_int32,
                                       c_float_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p]),
+    ("msw_rollout_metrics_launch", C.c_int, [C.c_int64, C.c_int32, c_int32_p, c_int32_p, c_int32_p, c_int32_p]),
     ("msw_flood_maps_update", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64,
                                         C.c_int64, c_float_p, C.c_int32, C.c_float, C.c_int32,
                                         C.POINTER(MswFloodMaps), C.c_void_p]),

@@ -31,10 +31,18 @@ def rollout_metrics(pred, real, ranges, thresholds=(0.05, 0.3), mass=None, strea
       rmse, mae             [S, 2]  get_rollout_loss(only_where_water=False)
       rmse_water, mae_water [S, 2]  get_rollout_loss(only_where_water=True)
       csi[thr], f1[thr]     [S, T]  get_CSI / get_F1 (NaN where the step has no flooded cell)
-    mass (optional): dict(area=[N] cell areas by graph row, node_bc=[rows per simulation],
-    bc=[per simulation [n_BC, >= T+1] boundary discharge], edge_bc_length=[per simulation
-    [n_BC] or scalar], temporal_res=minutes per step (scalar or per simulation)) adds
+    mass (optional): dict(area=[N] cell areas by graph row, node_bc=[per simulation, its BC
+    cells], bc=[per simulation [n_BC, >= T+1] boundary discharge], edge_bc_length=[per
+    simulation [n_BC] or scalar], temporal_res=minutes per step (scalar or per simulation)) adds
       mass_loss             [S, T-1]  get_mass_conservation_loss (x 1e-6 m^3, as it returns)
+    node_bc[g] holds GRAPH rows, the numbering of pred and area: for a batch the node_BC that
+    adapt_batch_training leaves (ptr[g] + the simulation's own node_BC, training/train.py:18),
+    e.g. ``[b.node_BC[b.node_BC_ptr == g] for g in range(S)]``.  The reference evaluates one
+    simulation at a time, where the two numberings coincide (its conservation_loss indexes
+    ``(area * delta_WD)[data.node_BC]`` in the numbering of the tensor it is given,
+    training/loss.py:161); for a batch that tensor is the whole [N, ...] and so are the rows.
+    A row outside simulation g's finest range raises ValueError.
+    A simulation with no finest rows gives NaN losses (0 / 0) and does not raise.
     """
     if not (pred.is_cuda and real.is_cuda):
         raise RuntimeError("rollout_metrics runs on the GPU (HIP kernel); tensors are on the CPU")
@@ -74,7 +82,7 @@ def rollout_metrics(pred, real, ranges, thresholds=(0.05, 0.3), mass=None, strea
         out["f1"][t] = (tp / (tp + 0.5 * (fn + fp))).float()           # miscellaneous.py:166
     out["counts"] = counts
     if mass is not None:
-        out["mass_loss"] = _mass_loss(pred, sums[..., 9], area, mass, S, T)
+        out["mass_loss"] = _mass_loss(pred, sums[..., 9], area, mass, S, T, ranges)
     return out
 
 
@@ -82,7 +90,7 @@ def _per_sim(v, S):
     return list(v) if isinstance(v, (list, tuple)) else [v] * S
 
 
-def _mass_loss(pred, vol, area, mass, S, T):
+def _mass_loss(pred, vol, area, mass, S, T, ranges):
     """(predicted volume change - inflow volume - change at the BC cells) / 1e6 per step
     t = 1..T-1 (conservation_loss, training/loss.py:120-169; inflow: get_inflow_volume,
     utils/dataset.py:577-591, with BC averaged over [t, t+1], miscellaneous.py:119-121)."""
@@ -93,7 +101,11 @@ def _mass_loss(pred, vol, area, mass, S, T):
     tres = _per_sim(mass.get("temporal_res", 1), S)
     lens = _per_sim(mass["edge_bc_length"], S)
     for g in range(S):
-        rows = torch.as_tensor(mass["node_bc"][g], dtype=torch.long, device=pred.device).reshape(-1)
+        rows = torch.as_tensor(mass["node_bc"][g], dtype=torch.long).reshape(-1)
+        if rows.numel() and not (ranges[g][0] <= int(rows.min()) and int(rows.max()) < ranges[g][1]):
+            raise ValueError(f"mass['node_bc'][{g}] must hold graph rows inside simulation {g}'s finest range "
+                             f"{tuple(ranges[g])} (for a batch: node_BC as adapt_batch_training leaves it)")
+        rows = rows.to(pred.device)
         h = pred[rows, 0, :].double()                                  # [n_BC, T]
         corr = (area[rows].double()[:, None] * (h[:, 1:] - h[:, :-1])).sum(0)
         bc = torch.as_tensor(mass["bc"][g]).to(pred.device, torch.float64)
