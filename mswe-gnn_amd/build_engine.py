@@ -66,7 +66,10 @@ def build(force=False, verbose=True, variant=""):
              # test_build_variant_matches_default_bitwise[valubase]
              "valubase": ["-DMSW_PRELU_MAX=0", "-DMSW_EDGE_FULL=0"],
              # plain stores in place of the large-mesh launches' streaming stores
-             "nostream": ["-DMSW_STREAM_ST=0"]}.get(variant, [])
+             "nostream": ["-DMSW_STREAM_ST=0"],
+             # kernel arguments fetched where they are first used instead of pinned at kernel
+             # entry (kernels/k_base.h MSW_PIN): tests/test_gpu_args_hoist.py
+             "lazyargs": ["-DMSW_ARGS_HOIST=0"]}.get(variant, [])
     os.makedirs(odir, exist_ok=True)
     os.makedirs(os.path.join(HERE, "lib"), exist_ok=True)
     out = lib_path(variant)

@@ -56,6 +56,93 @@ __device__ __forceinline__ void normalize_s(f32x4 (&sv)[NT]) {
   }
 }
 
+// ---------------------------------------------------------------------------- kernel arguments
+// Every step kernel takes one struct by value.  The compiler fetches its fields with scalar
+// loads where they are first used and waits for each before the branch or address that needs
+// it, and the argument segment is cold at kernel start: a wave would begin with a chain of
+// dependent trips to memory (xcd -> ntiles -> recs -> lane record -> gathers).  MSW_PIN names
+// up to 30 scalar fields (or small vectors of them, kernarg_vec) as the inputs of ONE empty asm
+// statement: all of them have to be in SGPRs there, so their loads are issued back to back and
+// one wait covers them.  (One statement per field does not do it: an asm statement is a
+// scheduling barrier, and the loads of the next one stay behind it.)  It emits no instruction
+// of its own.  A kernel pins what it needs to reach its first vector loads at its entry, and the
+// descriptor fields its MFMA chain reads later in a second statement behind the tile's gathers,
+// whose flight that round trip then overlaps.  MSW_ARGS_HOIST=0: compiled away (A/B build
+// variant "lazyargs"; bit-identical, tests/test_gpu_args_hoist.py).  tools/kernarg_census.py
+// counts the round trips per kernel.
+#ifndef MSW_ARGS_HOIST
+#define MSW_ARGS_HOIST 1
+#endif
+#define MSW_PIN_OP_1(a) "s"(a)
+#define MSW_PIN_OP_2(a, ...) "s"(a), MSW_PIN_OP_1(__VA_ARGS__)
+#define MSW_PIN_OP_3(a, ...) "s"(a), MSW_PIN_OP_2(__VA_ARGS__)
+#define MSW_PIN_OP_4(a, ...) "s"(a), MSW_PIN_OP_3(__VA_ARGS__)
+#define MSW_PIN_OP_5(a, ...) "s"(a), MSW_PIN_OP_4(__VA_ARGS__)
+#define MSW_PIN_OP_6(a, ...) "s"(a), MSW_PIN_OP_5(__VA_ARGS__)
+#define MSW_PIN_OP_7(a, ...) "s"(a), MSW_PIN_OP_6(__VA_ARGS__)
+#define MSW_PIN_OP_8(a, ...) "s"(a), MSW_PIN_OP_7(__VA_ARGS__)
+#define MSW_PIN_OP_9(a, ...) "s"(a), MSW_PIN_OP_8(__VA_ARGS__)
+#define MSW_PIN_OP_10(a, ...) "s"(a), MSW_PIN_OP_9(__VA_ARGS__)
+#define MSW_PIN_OP_11(a, ...) "s"(a), MSW_PIN_OP_10(__VA_ARGS__)
+#define MSW_PIN_OP_12(a, ...) "s"(a), MSW_PIN_OP_11(__VA_ARGS__)
+#define MSW_PIN_OP_13(a, ...) "s"(a), MSW_PIN_OP_12(__VA_ARGS__)
+#define MSW_PIN_OP_14(a, ...) "s"(a), MSW_PIN_OP_13(__VA_ARGS__)
+#define MSW_PIN_OP_15(a, ...) "s"(a), MSW_PIN_OP_14(__VA_ARGS__)
+#define MSW_PIN_OP_16(a, ...) "s"(a), MSW_PIN_OP_15(__VA_ARGS__)
+#define MSW_PIN_OP_17(a, ...) "s"(a), MSW_PIN_OP_16(__VA_ARGS__)
+#define MSW_PIN_OP_18(a, ...) "s"(a), MSW_PIN_OP_17(__VA_ARGS__)
+#define MSW_PIN_OP_19(a, ...) "s"(a), MSW_PIN_OP_18(__VA_ARGS__)
+#define MSW_PIN_OP_20(a, ...) "s"(a), MSW_PIN_OP_19(__VA_ARGS__)
+#define MSW_PIN_OP_21(a, ...) "s"(a), MSW_PIN_OP_20(__VA_ARGS__)
+#define MSW_PIN_OP_22(a, ...) "s"(a), MSW_PIN_OP_21(__VA_ARGS__)
+#define MSW_PIN_OP_23(a, ...) "s"(a), MSW_PIN_OP_22(__VA_ARGS__)
+#define MSW_PIN_OP_24(a, ...) "s"(a), MSW_PIN_OP_23(__VA_ARGS__)
+#define MSW_PIN_OP_25(a, ...) "s"(a), MSW_PIN_OP_24(__VA_ARGS__)
+#define MSW_PIN_OP_26(a, ...) "s"(a), MSW_PIN_OP_25(__VA_ARGS__)
+#define MSW_PIN_OP_27(a, ...) "s"(a), MSW_PIN_OP_26(__VA_ARGS__)
+#define MSW_PIN_OP_28(a, ...) "s"(a), MSW_PIN_OP_27(__VA_ARGS__)
+#define MSW_PIN_OP_29(a, ...) "s"(a), MSW_PIN_OP_28(__VA_ARGS__)
+#define MSW_PIN_OP_30(a, ...) "s"(a), MSW_PIN_OP_29(__VA_ARGS__)
+#define MSW_PIN_SEL( \
+    _1, _2, _3, _4, _5, _6, _7, _8, _9, _10, _11, _12, _13, _14, _15, _16, _17, _18, _19, _20, _21, \
+    _22, _23, _24, _25, _26, _27, _28, _29, _30, NAME, ...) \
+  NAME
+#define MSW_PIN_OPS(...) \
+  MSW_PIN_SEL( \
+      __VA_ARGS__, MSW_PIN_OP_30, MSW_PIN_OP_29, MSW_PIN_OP_28, MSW_PIN_OP_27, MSW_PIN_OP_26, \
+      MSW_PIN_OP_25, MSW_PIN_OP_24, MSW_PIN_OP_23, MSW_PIN_OP_22, MSW_PIN_OP_21, MSW_PIN_OP_20, \
+      MSW_PIN_OP_19, MSW_PIN_OP_18, MSW_PIN_OP_17, MSW_PIN_OP_16, MSW_PIN_OP_15, MSW_PIN_OP_14, \
+      MSW_PIN_OP_13, MSW_PIN_OP_12, MSW_PIN_OP_11, MSW_PIN_OP_10, MSW_PIN_OP_9, MSW_PIN_OP_8, \
+      MSW_PIN_OP_7, MSW_PIN_OP_6, MSW_PIN_OP_5, MSW_PIN_OP_4, MSW_PIN_OP_3, MSW_PIN_OP_2, \
+      MSW_PIN_OP_1) \
+  (__VA_ARGS__)
+#define MSW_PIN(...)                                                      \
+  do {                                                                    \
+    if constexpr (MSW_ARGS_HOIST) asm volatile("" ::MSW_PIN_OPS(__VA_ARGS__)); \
+  } while (0)
+// an operand only some instantiations need (the grid stride of the loop variants, the model
+// width of the run-time-activation ones): the others name a field pinned anyway, which costs nothing
+#define MSW_PIN_IF(cond, x, other) ((cond) ? (int)(x) : (int)(other))
+// field lists to splice into MSW_PIN
+// an epilogue's switches: what epi_prefetch and node_epilogue branch on
+// (np.h1t with them: the compiler fetches the four adjacent ints in one load, and a dword of
+// such a load that nothing uses has its register reused by a later load, which then waits for
+// the first to land -- a second round trip; the same for every "with its neighbours" below)
+#define MSW_ARGS_EPI_SW(e) (e).np.a_u, (e).np.a_v, (e).np.a_o, (e).np.h1t, (e).uu_a, (e).dec.on
+#define MSW_ARGS_EPI_REST(e) (e).post_act, (e).post_slope, (e).uu_h1t
+// one MFMA chain's layer descriptors (operand and bias offsets, slopes)
+#define MSW_ARGS_MLP(m)                                                                                        \
+  (m).n, (m).l[0].a_off, (m).l[0].b_off, (m).l[0].slope, (m).l[1].a_off, (m).l[1].b_off, (m).l[1].slope,       \
+      (m).l[2].a_off, (m).l[2].b_off, (m).l[2].slope, (m).l[3].a_off, (m).l[3].b_off, (m).l[3].slope
+// N consecutive ints of the argument struct as one SGPR tuple (one s_load_dwordxN)
+template <int N>
+using i32xN = int __attribute__((ext_vector_type(N)));
+template <int N>
+__device__ __forceinline__ i32xN<N> kernarg_vec(const void* p) {
+  typedef i32xN<N> __attribute__((aligned(4))) V;
+  return *reinterpret_cast<const V*>(p);
+}
+
 __device__ __forceinline__ int wave_id() { return threadIdx.x >> 6; }
 // XCD packing (Common::xcd = k > 0, small one-round grids): the launch has 8x the workgroups
 // it needs and only those the dispatcher places on XCDs 0 .. k-1 (workgroup i -> XCD i % 8)
@@ -302,8 +389,8 @@ struct EpiPre {
 // column (kMaxDyn x kMaxDyn / 2 selects), at the cost of kMaxDyn / 2 more live registers (the
 // four-rank F = 64 encoder, at its 128-register cap, keeps bcv)
 template <int NT, bool BYCOL = false>
-__device__ __forceinline__ void bc_prefetch(EpiPre<NT>& p, const DecDesc& d, const Common& c) {
-  const RolloutIO* io = d.io;
+__device__ __forceinline__ void bc_prefetch(EpiPre<NT>& p, const RolloutIO& iov, const Common& c) {
+  const RolloutIO* io = &iov;  // the launch's copy of the record (read once at kernel entry)
   const bool on = p.bc >= 0 && p.step + 1 < io->bc_tstride;
   const float* bp = on ? io->bc + (size_t)p.bc * c.p * io->bc_tstride + p.step + 1 : c.zrow;
   const int ts = on ? io->bc_tstride : 0;

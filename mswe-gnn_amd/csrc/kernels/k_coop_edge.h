@@ -395,6 +395,22 @@ __global__ __launch_bounds__(64 * kWaves) void k_edge_coop(EdgeHopArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int lane = threadIdx.x & 63, g = lane >> 4, j = lane & 15, w = wave_id();
   const int grp = w / P, r = w % P;
+  if constexpr (FUSE == 1) {
+    if constexpr (LST != 0)
+      MSW_PIN(MSW_ARGS_EDGE(a), a.pool.slots, a.pool.in, MSW_ARGS_EPI_SW(a.epi));
+    else
+      MSW_PIN(MSW_ARGS_EDGE(a), a.pool.slots, a.pool.in);
+  } else if constexpr (FUSE == 2) {
+    if constexpr (LST != 0)
+      MSW_PIN(MSW_ARGS_EDGE(a), a.pool.parent, a.pool.cpad, a.pool.Uu, a.pool.Vu, a.pool.xc, a.pool.skip, a.pool.h1t,
+              MSW_ARGS_EPI_SW(a.epi));
+    else
+      MSW_PIN(MSW_ARGS_EDGE(a), a.pool.parent, a.pool.cpad, a.pool.Uu, a.pool.Vu, a.pool.xc, a.pool.skip, a.pool.h1t);
+  } else if constexpr (LST != 0) {
+    MSW_PIN(MSW_ARGS_EDGE(a), MSW_ARGS_EDGE_ROWS(a), MSW_ARGS_EPI_SW(a.epi));
+  } else {
+    MSW_PIN(MSW_ARGS_EDGE(a), MSW_ARGS_EDGE_ROWS(a));
+  }
   const int xb = logical_block(a.c);
   if (xb < 0) return;
   const int tile = xb * G + grp;
@@ -416,6 +432,12 @@ __global__ __launch_bounds__(64 * kWaves) void k_edge_coop(EdgeHopArgs a) {
       edge_unpool_load<NT, LST>(q, uin, a, live ? tile : 0, j, g, r);
     else
       edge_hop_load<NT, LST, FULL>(q, a, live ? tile : 0, j, g);  // dead groups compute tile 0, store nothing
+    // behind the gathers: the staging's and the chain's fields
+    if constexpr (FUSE != 0)
+      MSW_PIN(MSW_ARGS_EDGE_STAGE(a), MSW_ARGS_EDGE_CHAIN(a), a.pool.np.a_u, a.pool.np.a_v, a.pool.np.a_o, a.pool.np.h1t);
+    else
+      MSW_PIN(MSW_ARGS_EDGE_STAGE(a), MSW_ARGS_EDGE_CHAIN(a));
+    if constexpr (LST != 0) MSW_PIN(MSW_ARGS_EPI_REST(a.epi));
     const bool split = a.reg.split < a.reg_nf;
     stage_glds<kWaves>(smem, a.c.W, a.reg, 0, a.reg.split);
     __syncthreads();
@@ -590,6 +612,16 @@ __global__ __launch_bounds__(64 * kWaves) void k_edge_coop4(EdgeHopArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int lane = threadIdx.x & 63, g = lane >> 4, j = lane & 15, w = wave_id();
   const int grp = w / P, r = w % P;
+  if constexpr (FUSE == 1) {
+    if constexpr (LST != 0)
+      MSW_PIN(MSW_ARGS_EDGE(a), a.pool.slots, a.pool.in, MSW_ARGS_EPI_SW(a.epi));
+    else
+      MSW_PIN(MSW_ARGS_EDGE(a), a.pool.slots, a.pool.in);
+  } else if constexpr (LST != 0) {
+    MSW_PIN(MSW_ARGS_EDGE(a), MSW_ARGS_EDGE_ROWS(a), MSW_ARGS_EPI_SW(a.epi));
+  } else {
+    MSW_PIN(MSW_ARGS_EDGE(a), MSW_ARGS_EDGE_ROWS(a));
+  }
   const int xb = logical_block(a.c);
   if (xb < 0) return;
   const int tile0 = xb * G + grp;
@@ -621,6 +653,13 @@ __global__ __launch_bounds__(64 * kWaves) void k_edge_coop4(EdgeHopArgs a) {
   else
     edge_hop_load<NT, LST>(q, a, tile, j, g);
   const Lanes& L = q.L;
+  // behind the gathers: the staging's and the chain's fields
+  if constexpr (FUSE != 0)
+    MSW_PIN(a.wdirect, MSW_ARGS_EDGE_STAGE(a), MSW_ARGS_EDGE_CHAIN(a), a.pool.np.a_u, a.pool.np.a_v, a.pool.np.a_o,
+            a.pool.np.h1t);
+  else
+    MSW_PIN(a.wdirect, MSW_ARGS_EDGE_STAGE(a), MSW_ARGS_EDGE_CHAIN(a));
+  if constexpr (LST != 0) MSW_PIN(MSW_ARGS_EPI_REST(a.epi));
   // the MLP region: staged in LDS, or (wdirect: two workgroups per CU) read from its blob copy
   if (a.reg.len > 0 && !a.wdirect) stage_glds<kWaves>(smem, c.W, a.reg, 0, a.reg.len);
   // the MLP operands through a pointer the compiler can prove to be LDS when staged (the

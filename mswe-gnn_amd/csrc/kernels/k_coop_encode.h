@@ -115,18 +115,33 @@ __global__ __launch_bounds__(64 * WV) __attribute__((amdgpu_waves_per_eu(4))) vo
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int lane = threadIdx.x & 63, g = lane >> 4, j = lane & 15, w = wave_id();
   const int grp = w / P, r = w % P;
+  // (the decoding encoders are at their register limit -- F = 64 at its 128-register cap, F = 32
+  // three SGPRs short of spilling: scalars only, the search stays)
+  constexpr bool TAB = !DEC;
+  constexpr bool SCAL = MSW_ARGS_HOIST && !DEC && NT == 4;  // n0 / ns as scalars (k_encode.h MSW_ARGS_ENC_N)
+  EncTables<kStaged<NT>> tb{};
+  if constexpr (MSW_ARGS_HOIST && TAB && !SCAL) tb = enc_tables<kStaged<NT>>(a);
+  if constexpr (DEC)
+    MSW_PIN(MSW_ARGS_ENC(a), MSW_ARGS_ENC_DEC(a));
+  else if constexpr (kStaged<NT>)
+    MSW_PIN(MSW_ARGS_ENC(a), MSW_ARGS_ENC_TAB(tb), MSW_ARGS_ENC_REG(tb));
+  else
+    MSW_PIN(MSW_ARGS_ENC(a), MSW_ARGS_ENC_N(a));
   MSW_MARK(a.c, 0);
   Common c = a.c;
-  const int dstep = DEC ? a.dec.io->step : -1;
+  RolloutIO iocopy{};  // as k_encode: the I/O record, read once
+  if constexpr (DEC && MSW_ARGS_HOIST) iocopy = *a.dec.io;
+  const RolloutIO& iov = (DEC && !MSW_ARGS_HOIST) ? *a.dec.io : iocopy;
+  const int dstep = DEC ? iov.step : -1;
   if (!a.dec.on && a.io && blockIdx.x == 0 && threadIdx.x == 0) a.io->step += 1;
   // one chunk of G row tiles per workgroup (scale starts are 64-aligned: one scale)
   const int rb = blockIdx.x * (G * kRowsPerWave);
-  int s = 0;
-  while (s + 1 < a.S && rb >= a.n0[s + 1]) ++s;
+  const EncScale sc = SCAL ? enc_scale_scalars(a, rb) : TAB ? enc_scale(a, tb, rb) : enc_scale(a, rb);
+  const int s = sc.s;
   const int n = rb + grp * kRowsPerWave + j;
-  const bool valid = (n - a.n0[s]) < a.ns[s];
+  const bool valid = (n - sc.n0) < sc.ns;
   const int ext = a.c.perm ? a.c.perm[n] : n;
-  const int xrow = a.x_internal ? (valid ? n : a.n0[s]) : (valid ? ext : 0);
+  const int xrow = a.x_internal ? (valid ? n : sc.n0) : (valid ? ext : 0);
   const float* xr = a.x + (size_t)xrow * a.c.nnf;
   const int nstat = a.c.nstat_raw;
   float raw[4], dyn[4];
@@ -152,14 +167,15 @@ __global__ __launch_bounds__(64 * WV) __attribute__((amdgpu_waves_per_eu(4))) vo
   }
   wlv = xr[nstat - 1] + xr[a.c.nnf - 2];
   if constexpr (kBcHoist<NT>) {  // see k_base.h kBcHoist
+    if constexpr (DEC) MSW_PIN(iov.step, iov.bc, iov.bc_tstride, iov.type_bc);
     if (DEC && dstep >= 0) {
       pre.step = dstep;
-      bc_prefetch<NT>(pre, a.dec, c);
+      bc_prefetch<NT>(pre, iov, c);
     }
   }
   MSW_MARK(c, 1);
   if constexpr (kStaged<NT>) {
-    stage_glds<WV>(smem, a.c.W, a.sreg[s], 0, a.sreg[s].len);
+    stage_glds<WV>(smem, a.c.W, sc.reg, 0, sc.reg.len);
     __syncthreads();
   }
   const float* Wl = kStaged<NT> ? (const float*)smem : c.W;
@@ -181,7 +197,7 @@ __global__ __launch_bounds__(64 * WV) __attribute__((amdgpu_waves_per_eu(4))) vo
     dec_mlp.load(a.dec.dec, Wl, r, lane, g);
     if constexpr (!kBcHoist<NT>) {
       pre.step = dstep;
-      bc_prefetch<NT>(pre, a.dec, c);
+      bc_prefetch<NT>(pre, iov, c);
     }
     float nd[kMaxDyn];
     {
@@ -224,11 +240,11 @@ __global__ __launch_bounds__(64 * WV) __attribute__((amdgpu_waves_per_eu(4))) vo
       np_project_coop<NT, NT, P, kEncProjAhead>(xs, xd, a.np0, Wl, n, valid, r, lane, g);
   }
   MSW_MARK(c, 8);
-  if (a.vu_a[s] >= 0) {
+  if (sc.vu_a >= 0) {
     if (a.vu_h1t == T2)
-      proj_store_part<NT, T2 / P, kEncProjAhead>(xs, Wl + a.vu_a[s], r, a.Vu, n, T2, valid, lane, g);
+      proj_store_part<NT, T2 / P, kEncProjAhead>(xs, Wl + sc.vu_a, r, a.Vu, n, T2, valid, lane, g);
     else
-      proj_store_part<NT, NT / P, kEncProjAhead>(xs, Wl + a.vu_a[s], r, a.Vu, n, NT, valid, lane, g);
+      proj_store_part<NT, NT / P, kEncProjAhead>(xs, Wl + sc.vu_a, r, a.Vu, n, NT, valid, lane, g);
   }
   MSW_MARK(c, 9);
 }

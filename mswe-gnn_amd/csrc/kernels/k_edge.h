@@ -274,6 +274,20 @@ __device__ __forceinline__ void edge_hop_finish(f32x4 (&res)[NT], const EdgeHopR
     store_row<NT>(a.out + L.n * F, res, NT, g);
   }
 }
+// entry fields of the edge kernels (k_base.h MSW_PIN): to the lane record, the FULL-shape test
+// and the tile's gathers (ROWS: the rows a fused pooling / unpooling load replaces); STAGE: the
+// weight region, staged behind the gathers (before them in the grid-stride loop); CHAIN: what
+// the MLP chain reads, pinned behind the gathers
+#define MSW_ARGS_EDGE(a)                                                                                    \
+  (a).c.xcd, (a).ntiles, (a).recs, (a).n0, (a).step_inc, (a).c.W, (a).c.zrow, (a).filt_a, (a).Pe, (a).h1t, \
+      (a).xs, (a).own_zero, (a).skip, (a).grad, (a).upwind, (a).last
+#define MSW_ARGS_EDGE_ROWS(a) (a).U, (a).V, (a).in
+#define MSW_ARGS_EDGE_STAGE(a) (a).reg.off, (a).reg.len, (a).reg.split, (a).reg_nf
+// ACT (act < 0): the model width, which mask_pad reads; DEC: the decoder's shape fields, which
+// the compiler fetches ahead of the tile's loads in the kernels with an epilogue
+#define MSW_ARGS_EDGE_ACT(a, act) MSW_PIN_IF((act) < 0, (a).c.fl, (a).ntiles)
+#define MSW_ARGS_EDGE_DEC(a) (a).c.nnf, (a).c.dyn, (a).c.p, (a).c.nstat_raw
+#define MSW_ARGS_EDGE_CHAIN(a) (a).b1_off, (a).act1, (a).slope1, (a).normalize, MSW_ARGS_MLP((a).rest)
 template <int NT, int ACT, bool LOOP, int LST>
 __global__ __launch_bounds__((64 * edge_waves<NT, LOOP, LST>())) __attribute__((amdgpu_waves_per_eu(edge_eu<NT, LOOP, LST>())))
 void k_edge_hop(EdgeHopArgs a) {
@@ -284,6 +298,23 @@ void k_edge_hop(EdgeHopArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int lane = threadIdx.x & 63, g = lane >> 4, j = lane & 15, w = wave_id();
   const int stride = gridDim.x * WV;
+  if constexpr (LOOP && NT == 4) {  // (more would cost the F = 64 loop scratch)
+    if constexpr (LST != 0)
+      MSW_PIN(stride, a.c.xcd, a.ntiles, a.recs, a.n0, a.step_inc, a.c.W, a.filt_a, a.reg.off, a.reg.len, a.reg.split,
+              MSW_ARGS_EDGE_DEC(a));
+    else
+      MSW_PIN(stride, a.c.xcd, a.ntiles, a.recs, a.n0, a.step_inc, a.c.W, a.filt_a, a.reg.off, a.reg.len, a.reg.split);
+  } else if constexpr (LOOP) {  // (no second statement: the grid-stride loop has no SGPRs to spare)
+    if constexpr (LST != 0)  // (the rows' bases are first read inside the loop: left lazy)
+      MSW_PIN(stride, a.c.xcd, a.ntiles, a.recs, a.n0, a.step_inc, a.c.W, a.filt_a, a.Pe, a.h1t, a.own_zero, a.skip, a.grad,
+              a.upwind, a.last, a.reg.off, a.reg.len, a.reg.split, MSW_ARGS_EPI_SW(a.epi), MSW_ARGS_EDGE_DEC(a));
+    else
+      MSW_PIN(MSW_ARGS_EDGE(a), MSW_ARGS_EDGE_ROWS(a), MSW_ARGS_EDGE_STAGE(a));
+  } else if constexpr (LST != 0) {
+    MSW_PIN(MSW_ARGS_EDGE(a), MSW_ARGS_EDGE_ROWS(a), MSW_ARGS_EPI_SW(a.epi), MSW_ARGS_EDGE_ACT(a, ACT), MSW_ARGS_EDGE_DEC(a));
+  } else {
+    MSW_PIN(MSW_ARGS_EDGE(a), MSW_ARGS_EDGE_ROWS(a), MSW_ARGS_EDGE_ACT(a, ACT));
+  }
   const int xb = logical_block(a.c);
   if (xb < 0) return;
   int tile = xb * WV + w;
@@ -300,6 +331,10 @@ void k_edge_hop(EdgeHopArgs a) {
       const bool live = tile < a.ntiles;
       EdgeHopRows<NT> r;
       edge_hop_load<NT, LST, FULL>(r, a, live ? tile : 0, j, g);  // idle waves stay in bounds
+      if constexpr (LST != 0)  // behind the gathers
+        MSW_PIN(MSW_ARGS_EDGE_STAGE(a), MSW_ARGS_EDGE_CHAIN(a), MSW_ARGS_EPI_REST(a.epi));
+      else
+        MSW_PIN(MSW_ARGS_EDGE_STAGE(a), MSW_ARGS_EDGE_CHAIN(a));
       MSW_MARK(c, 1);
       // weights the MLP needs now; the epilogue's operands (unpool / K = 1 projections)
       // stream into LDS behind the MLP and are waited for at the epilogue barrier
@@ -414,7 +449,14 @@ void k_edge_mlp(EdgeHopArgs a) {
   const int w = wave_id();
   const int stride = gridDim.x * kMlpWaves;
   const int ch0 = blockIdx.x * kMlpWaves + w;
-  if (a.step_inc && blockIdx.x == 0 && threadIdx.x == 0) *a.step_inc += 1;
+  if constexpr (NT == 4)  // (F = 64, at its SGPR limit: what leads to the first chunk's loads only)
+    MSW_PIN(stride, a.nchunks, a.chunks, a.c.W, a.U, a.V, a.Pe, a.h1t, a.reg.off, a.reg.len);
+  else
+    MSW_PIN(stride, a.nchunks, a.chunks, a.n0, a.step_inc, a.c.W, a.c.zrow, a.U, a.V, a.Pe, a.h1t, a.reg.off, a.reg.len,
+            a.stagger, a.s);
+  if constexpr (!MSW_ARGS_HOIST) {  // the lazy build keeps the increment at the kernel's top
+    if (a.step_inc && blockIdx.x == 0 && threadIdx.x == 0) *a.step_inc += 1;
+  }
   // FULL: a 2F-wide first layer with an edge term (k_edge_hop's edge_full): no per-element
   // selects on the run-time shape flags, and the first chunk's rows are gathered while the
   // weight staging is in flight (issued after it: the in-order memory counter then waits for
@@ -489,6 +531,11 @@ void k_edge_mlp(EdgeHopArgs a) {
     e0 = f0.e;
 #pragma unroll
     for (int t = 0; t < T2; ++t) H0[t] = (f0.u[t] + f0.v[t]) + f0.p[t];
+  }
+  // (behind the first chunk's loads: ahead of them, the branch cost the run-time-activation F = 64
+  // kernel a reload of its arguments and a second round trip; nothing in this launch reads the step)
+  if constexpr (MSW_ARGS_HOIST) {
+    if (a.step_inc && blockIdx.x == 0 && threadIdx.x == 0) *a.step_inc += 1;
   }
   if (a.reg.len > 0) __syncthreads();
   // stagger: the two waves of a SIMD (w, w + 4) otherwise run the same phase at the same time, so

@@ -3,6 +3,89 @@
 // comment for the register layout and conventions.
 #pragma once
 
+// ---------------------------------------------------------------------------- encoder arguments
+// The scale of the 64-row chunk that starts at row rb and that scale's fields.  k_encode_coop
+// selects them from the whole small per-scale arrays, which arrive with its other arguments
+// (EncTables, pinned at entry): a search loop and run-time-indexed argument reads were one
+// dependent trip to the cold argument segment each.  (Scale starts ascend, so the last scale
+// that starts at or before rb is the one the search found.)
+struct EncScale {
+  int s, n0, ns, vu_a;
+  WReg reg;
+};
+// (k_encode keeps the search: its grid-stride loop would hold the tables in 48 SGPRs, which it
+// does not have; STAGED = kStaged<NT>: the regions exist at F <= 32 only)
+template <bool STAGED>
+struct EncTables {  // EncodeArgs::n0 / ns / vu_a [0, 8) and sreg (3 ints per scale) as SGPR tuples
+  i32xN<8> n0, ns, vu;
+  i32xN<16> ra;
+  i32xN<8> rb;
+};
+template <>
+struct EncTables<false> {
+  i32xN<8> n0, ns, vu;
+};
+static_assert(kMaxScales == 8 && sizeof(WReg) == 12, "EncTables: eight scales, {off, len, split} regions");
+template <bool STAGED>
+__device__ __forceinline__ EncTables<STAGED> enc_tables(const EncodeArgs& a) {
+  if constexpr (STAGED)
+    return EncTables<true>{kernarg_vec<8>(a.n0), kernarg_vec<8>(a.ns), kernarg_vec<8>(a.vu_a), kernarg_vec<16>(a.sreg),
+                           kernarg_vec<8>(reinterpret_cast<const int*>(a.sreg) + 16)};
+  else
+    return EncTables<false>{kernarg_vec<8>(a.n0), kernarg_vec<8>(a.ns), kernarg_vec<8>(a.vu_a)};
+}
+// the lazy form: search, then run-time-indexed reads
+__device__ __forceinline__ EncScale enc_scale(const EncodeArgs& a, int rb) {
+  int s = 0;
+  while (s + 1 < a.S && rb >= a.n0[s + 1]) ++s;
+  return EncScale{s, a.n0[s], a.ns[s], a.vu_a[s], a.sreg[s]};
+}
+template <bool STAGED>
+__device__ __forceinline__ EncScale enc_scale(const EncodeArgs& a, const EncTables<STAGED>& t, int rb) {
+  if constexpr (!MSW_ARGS_HOIST) return enc_scale(a, rb);
+  EncScale e{0, t.n0[0], t.ns[0], t.vu[0], WReg{0, 0, 0}};
+  if constexpr (STAGED) e.reg = WReg{t.ra[0], t.ra[1], 0};
+#pragma unroll
+  for (int k = 1; k < kMaxScales; ++k) {
+    const bool in = k < a.S && rb >= t.n0[k];
+    e.s = in ? k : e.s;
+    e.n0 = in ? t.n0[k] : e.n0;
+    e.ns = in ? t.ns[k] : e.ns;
+    e.vu_a = in ? t.vu[k] : e.vu_a;
+    if constexpr (STAGED) {
+      const int off = 3 * k < 16 ? t.ra[3 * k < 16 ? 3 * k : 0] : t.rb[3 * k >= 16 ? 3 * k - 16 : 0];
+      const int len = 3 * k + 1 < 16 ? t.ra[3 * k + 1 < 16 ? 3 * k + 1 : 0] : t.rb[3 * k + 1 >= 16 ? 3 * k + 1 - 16 : 0];
+      e.reg.off = in ? off : e.reg.off;
+      e.reg.len = in ? len : e.reg.len;
+    }
+  }
+  return e;
+}
+// what both encoders read before their first row load; TAB: the per-scale tables
+#define MSW_ARGS_ENC(a)                                                                                       \
+  (a).Npad, (a).S, (a).x, (a).x_internal, (a).c.perm, (a).c.nnf, (a).c.nstat_raw, (a).c.dyn, (a).c.W, (a).io, \
+      (a).dec.on
+#define MSW_ARGS_ENC_DEC(a) (a).dec.io, (a).dec_in, (a).dec.bc_slot
+#define MSW_ARGS_ENC_TAB(t) (t).n0, (t).ns, (t).vu
+#define MSW_ARGS_ENC_REG(t) (t).ra, (t).rb
+// F = 64 (no regions): the scale starts and row counts as sixteen scalars -- the misaligned
+// 8-int tuples cost a second round trip there (they are assembled from two loads' pieces) --
+// and vu_a[s] read where it is used, at the kernel's end
+#define MSW_ARGS_ENC_N(a)                                                                                  \
+  (a).n0[0], (a).n0[1], (a).n0[2], (a).n0[3], (a).n0[4], (a).n0[5], (a).n0[6], (a).n0[7], (a).ns[0], (a).ns[1], \
+      (a).ns[2], (a).ns[3], (a).ns[4], (a).ns[5], (a).ns[6], (a).ns[7]
+__device__ __forceinline__ EncScale enc_scale_scalars(const EncodeArgs& a, int rb) {
+  EncScale e{0, a.n0[0], a.ns[0], 0, WReg{0, 0, 0}};
+#pragma unroll
+  for (int k = 1; k < kMaxScales; ++k) {
+    const bool in = k < a.S && rb >= a.n0[k];
+    e.s = in ? k : e.s;
+    e.n0 = in ? a.n0[k] : e.n0;
+    e.ns = in ? a.ns[k] : e.ns;
+  }
+  e.vu_a = a.vu_a[e.s];
+  return e;
+}
 // ---------------------------------------------------------------------------- encoder
 // Static / dynamic node encoders incl. the water-level feature (MSGNN.forward
 // gnn.py:284-294, GNN.forward :112-123) + projection of processor 0 + the x_s part of
@@ -18,11 +101,20 @@ __global__ __launch_bounds__(kBlock) void k_encode(EncodeArgs a) {
   constexpr int F = 16 * NT;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int lane = threadIdx.x & 63, g = lane >> 4, j = lane & 15;
+  if constexpr (DEC)
+    MSW_PIN(MSW_ARGS_ENC(a), MSW_ARGS_ENC_DEC(a));
+  else
+    MSW_PIN(MSW_ARGS_ENC(a));
   MSW_MARK(a.c, 0);
   Common c = a.c;
   // rollout mode: the step whose prediction this launch decodes (the previous one; -1 at
-  // step 0, whose state k_init_state wrote)
-  const int dstep = DEC ? a.dec.io->step : -1;
+  // step 0, whose state k_init_state wrote).  The I/O record is read once, whole, as soon as
+  // its pointer has arrived (nothing writes it during a decoding launch).
+  // (MSW_ARGS_HOIST=0: every field read through the pointer where it is used)
+  RolloutIO iocopy{};
+  if constexpr (DEC && MSW_ARGS_HOIST) iocopy = *a.dec.io;
+  const RolloutIO& iov = (DEC && !MSW_ARGS_HOIST) ? *a.dec.io : iocopy;
+  const int dstep = DEC ? iov.step : -1;
   // rollout mode, decoder in the last hops (large meshes): advance the step they read
   if (!a.dec.on && a.io && blockIdx.x == 0 && threadIdx.x == 0) a.io->step += 1;
   const int nchunks = a.Npad / kRowsPerBlock;
@@ -31,12 +123,12 @@ __global__ __launch_bounds__(kBlock) void k_encode(EncodeArgs a) {
   // the per-scale weight region is re-staged only when the scale changes
   for (int chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
     const int rb = chunk * kRowsPerBlock;
-    int s = 0;
-    while (s + 1 < a.S && rb >= a.n0[s + 1]) ++s;
+    const EncScale sc = enc_scale(a, rb);
+    const int s = sc.s;
     const int n = rb + wave_id() * kRowsPerWave + j;
-    const bool valid = (n - a.n0[s]) < a.ns[s];
+    const bool valid = (n - sc.n0) < sc.ns;
     const int ext = a.c.perm ? a.c.perm[n] : n;
-    const int xrow = a.x_internal ? (valid ? n : a.n0[s]) : (valid ? ext : 0);
+    const int xrow = a.x_internal ? (valid ? n : sc.n0) : (valid ? ext : 0);
     const float* xr = a.x + (size_t)xrow * a.c.nnf;
     const int nstat = a.c.nstat_raw;
     float raw[4], dyn[4];
@@ -61,16 +153,17 @@ __global__ __launch_bounds__(kBlock) void k_encode(EncodeArgs a) {
     }
     wlv = xr[nstat - 1] + xr[a.c.nnf - 2];  // water level = bed elevation + depth
     if constexpr (kBcHoist<NT>) {  // the next step's BC values before the weight staging
+      if constexpr (DEC) MSW_PIN(iov.step, iov.bc, iov.bc_tstride, iov.type_bc);
       if (DEC && dstep >= 0) {
         pre.step = dstep;
-        bc_prefetch<NT, true>(pre, a.dec, c);
+        bc_prefetch<NT, true>(pre, iov, c);
       }
     }
     MSW_MARK(c, 1);
     if constexpr (kStaged<NT>) {
       if (s != staged) {  // uniform across the workgroup: every wave walks the same chunks
         if (staged >= 0) __syncthreads();  // everyone is done with the old region
-        stage_glds(smem, a.c.W, a.sreg[s], 0, a.sreg[s].len);
+        stage_glds(smem, a.c.W, sc.reg, 0, sc.reg.len);
         __syncthreads();
         staged = s;
       }
@@ -81,7 +174,7 @@ __global__ __launch_bounds__(kBlock) void k_encode(EncodeArgs a) {
     if (DEC && dstep >= 0) {  // decode the previous step; the encoders read the updated state
       if constexpr (!kBcHoist<NT>) {
         pre.step = dstep;
-        bc_prefetch<NT, true>(pre, a.dec, c);
+        bc_prefetch<NT, true>(pre, iov, c);
       }
       float nd[kMaxDyn];
       decode_state<NT, ACT, true>(xu, a.dec, c, Wl, pre, n, valid, lane, g, nd);
@@ -115,7 +208,7 @@ __global__ __launch_bounds__(kBlock) void k_encode(EncodeArgs a) {
       np_project<NT, ST>(xs, xd, a.np0, Wl, n, valid, lane, g);
     }
     MSW_MARK(c, 8);
-    if (a.vu_a[s] >= 0) side_proj<NT, NT, ST>(xs, a.vu_h1t, Wl + a.vu_a[s], a.Vu, n, valid, lane, g);
+    if (sc.vu_a >= 0) side_proj<NT, NT, ST>(xs, a.vu_h1t, Wl + sc.vu_a, a.Vu, n, valid, lane, g);
   }
   MSW_MARK(c, 9);
 }
@@ -129,6 +222,8 @@ template <int NT, int ACT>
 __global__ __launch_bounds__(kBlock) void k_decode_fwd(DecodeArgs a) {
   constexpr int F = 16 * NT;
   const int lane = threadIdx.x & 63, g = lane >> 4, j = lane & 15;
+  MSW_PIN(a.Npad, a.in, a.c.perm, a.dec.X, a.c.nnf, a.c.dyn, a.c.W, a.dec.pre_act, a.dec.pre_slope, a.dec.resw_off,
+          a.dec.y, a.dec.dec.l[0].tin, MSW_ARGS_MLP(a.dec.dec));
   const int n = wave_row0() + j;
   if (wave_row0() >= a.Npad) return;  // whole wave past the rows
   const bool valid = n < a.Npad;

@@ -30,6 +30,12 @@ template <int NT, bool LAST>
 __device__ __forceinline__ void hop_load(HopRows<NT>& r, const HopArgs& a, int tile, int j, int g) {
   hop_gather<NT, LAST>(r, a, load_rec(a.recs, tile, j), tile, j, g);
 }
+// entry fields of the hops (k_base.h MSW_PIN): to the lane record and the gathers; the last hops'
+// also to the epilogue's prefetch and the weight staging
+#define MSW_ARGS_HOP(a) \
+  (a).c.xcd, (a).ntiles, (a).recs, (a).n0, (a).in, (a).s, (a).out, (a).c.W, (a).filt_a, (a).grad, (a).upwind
+#define MSW_ARGS_HOP_LAST(a) \
+  (a).xs, (a).reg.off, (a).reg.len, (a).reg.split, (a).last, (a).c.perm, (a).c.nnf, (a).c.dyn, MSW_ARGS_EPI_SW((a).epi)
 template <int NT, int ACT, bool LAST, bool LOOP>
 __global__ __launch_bounds__((64 * hop_waves<NT, LOOP>())) void k_hop(HopArgs a) {
 #pragma clang fp contract(off)
@@ -40,6 +46,14 @@ __global__ __launch_bounds__((64 * hop_waves<NT, LOOP>())) void k_hop(HopArgs a)
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int lane = threadIdx.x & 63, g = lane >> 4, j = lane & 15, w = wave_id();
   const int stride = gridDim.x * WV;
+  if constexpr (LAST && LOOP) {
+    // (the grid-stride last hop is out of SGPRs: what leads to the staging and the first record only)
+    MSW_PIN(stride, a.c.xcd, a.ntiles, a.recs, a.n0, a.c.W, a.filt_a, a.reg.off, a.reg.len, a.reg.split);
+  } else if constexpr (LAST) {
+    MSW_PIN(MSW_ARGS_HOP(a), MSW_ARGS_HOP_LAST(a));
+  } else {
+    MSW_PIN(MSW_ARGS_HOP(a));
+  }
   const int xb = logical_block(a.c);
   if (xb < 0) return;
   int tile = xb * WV + w;
@@ -47,6 +61,9 @@ __global__ __launch_bounds__((64 * hop_waves<NT, LOOP>())) void k_hop(HopArgs a)
   MSW_MARK(c, 0);
   f32x4 wf[NT][NT];
   load_filter<NT>(wf, c.W, a.filt_a, lane);  // blob offset: not part of the LDS region
+  // the grid-stride last hop: the filter load is issued before the epilogue's argument reads, which
+  // the compiler moves out of the tile loop to here (several dependent trips in the F = 64 kernel)
+  if constexpr (MSW_ARGS_HOIST && LAST && LOOP) __builtin_amdgcn_sched_barrier(0);
   float* slab = &slab_all[w][0][0];
   auto core = [&](const HopRows<NT>& r, int j, int lane, int g, f32x4 (&res)[NT]) {
     float* my = slab + j * XS;
@@ -78,6 +95,7 @@ __global__ __launch_bounds__((64 * hop_waves<NT, LOOP>())) void k_hop(HopArgs a)
     const bool live = tile < a.ntiles;
     HopRows<NT> r;
     hop_load<NT, LAST>(r, a, live ? tile : 0, j, g);
+    if constexpr (LAST) MSW_PIN(MSW_ARGS_EPI_REST(a.epi));  // behind the gathers
     MSW_MARK(c, 1);
     // the epilogue's operands stream into LDS alongside the tile's gathers
     if constexpr (LAST && kStaged<NT>) stage_glds<WV>(smem, a.c.W, a.reg, 0, a.reg.len);
@@ -151,6 +169,7 @@ __global__ __launch_bounds__(64 * kRowHopWaves) void k_hop_rows(HopArgs a) {
   [[maybe_unused]] const int lane = threadIdx.x & 63;
   const int w = wave_id();
   const int stride = gridDim.x * kRowHopWaves;
+  MSW_PIN(stride, a.nrows, a.rptr, a.redge, a.n0, a.in, a.s, a.out, a.c.W, a.filt_a, a.grad, a.upwind);
   const int ntile = (a.nrows + kRowsPerWave - 1) / kRowsPerWave;
   f32x4 wf[NT][NT];  // the filter in registers (in LDS: equal, profiles/r03/ab_rows_variants.jsonl)
   load_filter<NT>(wf, a.c.W, a.filt_a, lane);
@@ -236,6 +255,7 @@ __global__ __launch_bounds__(kBlock) void k_hop_split(HopArgs a) {
   __shared__ __attribute__((aligned(16))) f32x4 ax[G][NT][64];          // aggregated messages
   const int lane = threadIdx.x & 63, g = lane >> 4, j = lane & 15, w = wave_id();
   const int grp = w / 2, r = w % 2, t0 = r * TH;
+  MSW_PIN(MSW_ARGS_HOP(a));
   const int xb = logical_block(a.c);
   if (xb < 0) return;
   const int tile = xb * G + grp;
@@ -403,6 +423,7 @@ __global__ __launch_bounds__(kBlock) void k_hop_coop(HopArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int lane = threadIdx.x & 63, g = lane >> 4, j = lane & 15, w = wave_id();
   const int grp = w / P, r = w % P;
+  MSW_PIN(MSW_ARGS_HOP(a), MSW_ARGS_HOP_LAST(a));
   const int xb = logical_block(a.c);
   if (xb < 0) return;
   const int tile = xb * G + grp;
@@ -419,6 +440,7 @@ __global__ __launch_bounds__(kBlock) void k_hop_coop(HopArgs a) {
   }
   HopRows<NT> q;
   hop_load<NT, true>(q, a, live ? tile : 0, j, g);  // dead groups compute tile 0, store nothing
+  MSW_PIN(MSW_ARGS_EPI_REST(a.epi));  // behind the gathers
   if constexpr (kStaged<NT>) stage_glds<kWaves>(smem, a.c.W, a.reg, 0, a.reg.len);  // epilogue operands
   const Lanes& L = q.L;
   float* slab = &slab_all[w][0][0];

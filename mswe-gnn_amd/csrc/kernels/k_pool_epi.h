@@ -17,6 +17,9 @@ __global__ __launch_bounds__((64 * waves_of<NT, LOOP>())) void k_pool(PoolArgs a
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int lane = threadIdx.x & 63, g = lane >> 4, j = lane & 15, w = wave_id();
   const int stride = gridDim.x * WV;
+  MSW_PIN(MSW_PIN_IF(LOOP, stride, a.ntiles), a.np.U, a.np.V, a.np.O,
+          a.c.xcd, a.ntiles, a.recs, a.n0, a.ns, a.in, a.xs, a.child, a.c.W, a.reg.off, a.reg.len, a.reg.split,
+          a.np.a_u, a.np.a_v, a.np.a_o, a.np.h1t);
   const int xb = logical_block(a.c);
   if (xb < 0) return;
   int tile = xb * WV + w;
@@ -107,6 +110,8 @@ __global__ __launch_bounds__(64 * WV) void k_pool_edge(PoolArgs a) {
   __shared__ __attribute__((aligned(16))) float slab_all[WV][kRowsPerWave][XS];
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int lane = threadIdx.x & 63, g = lane >> 4, j = lane & 15, w = wave_id();
+  MSW_PIN(a.c.xcd, a.ntiles, a.erecs, a.n0, a.in, a.xs, a.c.W, a.reg.off, a.reg.len, a.reg.split, a.np.a_u, a.np.a_v,
+          a.np.a_o, a.np.h1t);
   const int xb = logical_block(a.c);
   if (xb < 0) return;
   int tile = xb * (WV / P) + w / P;
@@ -161,14 +166,27 @@ __global__ __launch_bounds__(64 * WV) void k_pool_edge(PoolArgs a) {
 // Same operations in the same order as the hop's own epilogue (bit-identical results).
 // LOOP: weights staged once per workgroup, the next tile's rows in flight while a tile
 // computes.
+// (F = 32, one tile per wave: five waves per SIMD, i.e. at most 96 registers, as the kernel had
+// before its arguments were pinned -- with them at hand earlier the run-time-activation
+// instantiation was scheduled into 100)
+template <int NT, bool LOOP>
+constexpr int epi_eu() { return NT == 2 && !LOOP ? 5 : 1; }
 template <int NT, int ACT, bool LOOP>
-__global__ __launch_bounds__((64 * waves_of<NT, LOOP>())) void k_epi(EpiArgs a) {
+__global__ __launch_bounds__((64 * waves_of<NT, LOOP>())) __attribute__((amdgpu_waves_per_eu(epi_eu<NT, LOOP>())))
+void k_epi(EpiArgs a) {
 #pragma clang fp contract(off)
   constexpr int WV = waves_of<NT, LOOP>();
   constexpr int F = 16 * NT;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int lane = threadIdx.x & 63, g = lane >> 4, j = lane & 15, w = wave_id();
   const int stride = gridDim.x * WV;
+  if constexpr (ACT < 0)  // (the run-time-activation kernels sit on an occupancy edge: entry fields only)
+    MSW_PIN(MSW_PIN_IF(LOOP, stride, a.ntiles), a.c.xcd, a.ntiles, a.n0, a.ns, a.in, a.xs, a.c.W, a.reg.off, a.reg.len,
+            a.reg.split);
+  else
+    MSW_PIN(MSW_PIN_IF(LOOP, stride, a.ntiles), MSW_PIN_IF(LOOP, a.max_blocks, a.ntiles),
+            MSW_PIN_IF(LOOP, a.fit_blocks, a.ntiles), a.c.xcd, a.ntiles, a.n0, a.ns, a.in, a.xs, a.out, a.c.W, a.reg.off,
+            a.reg.len, a.reg.split, a.c.perm, a.c.nnf, a.c.dyn, MSW_ARGS_EPI_SW(a.epi));
   const int xb = logical_block(a.c);
   if (xb < 0) return;
   int tile = xb * WV + w;
