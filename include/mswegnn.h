@@ -473,13 +473,105 @@ int msw_pool_mean_backward(int64_t num_nodes, int32_t F, const int32_t* coarse, 
                            const int32_t* fptr, const int32_t* fedge, const float* grad_out, float* grad_x,
                            void* stream);
 
+/* ---- Training: the loss of training_step and its gradient ---------------------
+ * Replaces loss_function (training/loss.py:76-169) and its autograd, which training_step calls
+ * after each of its R curriculum rollout steps (training/train.py:125-145): the masked multiscale
+ * RMSE / MAE over the finest scale of every graph, the velocity scaler, and the mass-conservation
+ * term conservation * |conservation_loss| with get_inflow_volume (utils/dataset.py:577-591).
+ * Stateless; every buffer is device memory the caller owns.  No atomics, no host synchronisation,
+ * no allocation: results are the same bit for bit from call to call.
+ *
+ * The rows of the ranges, taken in ascending order, form one list of `total` rows.  Forward,
+ * launch 1 (msw_train_loss_launch: `grid` workgroups of 256 threads, `iters` rounds): thread t of
+ * workgroup b takes list entries (b + k * grid) * 256 + t for k = 0, 1, ... and adds, in fp64 from
+ * +0.0 and in that order, per row i with d_h = (double)pred[i][0] - (double)real[i][0] and d_v
+ * likewise from column 1:
+ *     sel = !only_where_water || d_h != 0 || d_v != 0            (mask_on_water, loss.py:25-35)
+ *     n += sel;  S_h += sel ? d_h * d_h : 0;  S_v += sel ? d_v * d_v : 0       (MAE: |d_h|, |d_v|)
+ *     V += (double)area[i] * ((double)pred[i][0] - (double)input_h[i * stride])    (conservation != 0)
+ * The 64 lanes of a wave are combined by a butterfly (xor 32, 16, ... 1), the four waves in wave
+ * order, and the workgroup writes {n, S_h, S_v, V} to scratch[4 b ..].  Launch 2, one workgroup,
+ * all in fp64 and in this order:
+ *     n, S_h, S_v, V   = the workgroups' partials added in index order from +0.0
+ *     corr   = sum over k = 0 .. n_bc - 1 in order of (double)area[r] * ((double)pred[r][0] -
+ *              (double)input_h[r * stride]), r = node_bc[k]; entries outside [0, num_rows) are skipped
+ *     inflow = (sum over k in order of (double)bc[k] * (double)edge_bc_length[k]) * seconds_per_step
+ *     L_c    = sqrt(S_c / n)  (RMSE)   or   S_c / n  (MAE)                        c = h, v
+ *     data   = (L_h + vs * L_v) / (1 + vs)                                  vs = velocity_scaler
+ *     cons   = ((V - inflow) - corr) / 1e6 / num_graphs
+ *     loss   = conservation != 0 ? data + conservation * |cons| : data
+ *     coef_h = (1 / (1 + vs)) / (n * L_h),  coef_v = (vs / (1 + vs)) / (n * L_v)         (RMSE)
+ *     coef_h = (1 / (1 + vs)) / n,          coef_v = (vs / (1 + vs)) / n                 (MAE)
+ *     cc     = conservation * sgn(cons) / (1e6 * num_graphs)      sgn(x) = 1, -1 or x (0, NaN)
+ * With conservation == 0: V = corr = inflow = cons = cc = 0.  *loss_out = (float)loss and
+ *     record[12] = {n, S_h, S_v, V, corr, inflow, cons, loss, coef_h, coef_v, cc, data}.
+ * Backward, g = (double)*grad_out, per row i of [0, num_rows):
+ *     selected row of a range:  grad_pred[i][c] = (float)((g * coef_c) * d_c)               (RMSE)
+ *                               grad_pred[i][c] = (float)((g * coef_c) * sgn(d_c))          (MAE)
+ *     every other row: +0.0 in both columns (rows between the ranges included)
+ *     conservation != 0, with m_i = (float)((g * cc) * (double)area[i]):
+ *       range rows:   grad_pred[i][0] += m_i (an fp32 addition);   grad_input_h[i] = -m_i
+ *       other rows:   grad_input_h[i] = +0.0
+ *       then, one thread, for k = 0 .. n_bc - 1 in order, r = node_bc[k] in [0, num_rows):
+ *                     grad_pred[r][0] -= m_r;                      grad_input_h[r] += m_r
+ * (grad_input_h, [num_rows] floats with stride 1, is optional and written only when
+ * conservation != 0.)  The IEEE results of these formulas are the semantics: n = 0 gives a NaN
+ * loss and zero gradients, an RMSE column with S_c = 0 and n > 0 gives NaN gradients (0 * inf) on
+ * the selected rows, a NaN or inf in a range row selects the row and gives a NaN loss. */
+#define MSW_MAX_LOSS_RANGES 64
+#define MSW_TRAIN_LOSS_RECORD 12 /* doubles in `record` */
+enum msw_loss_type { MSW_LOSS_RMSE = 0, MSW_LOSS_MAE = 1 };
+typedef struct {
+  int64_t num_rows;                        /* N: rows of pred / real / area / input_h / the gradients */
+  int32_t num_ranges;                      /* 1..MSW_MAX_LOSS_RANGES */
+  int32_t type_loss;                       /* enum msw_loss_type */
+  int64_t ranges[MSW_MAX_LOSS_RANGES][2];  /* host values: [start, end) of the finest scale of every
+                                              graph (node_ptr[g][0], node_ptr[g][1]), or {0, N};
+                                              ascending and disjoint, empty ranges allowed */
+  int32_t only_where_water;
+  int32_t num_graphs;                      /* divides cons (a Batch's num_graphs; 1 for one Data) */
+  double velocity_scaler;
+  double conservation;                     /* 0: no mass term, the pointers below are not read */
+  double seconds_per_step;                 /* 60 * temporal_res (minutes) */
+  const float* area;                       /* device [N] cell areas (data.area) */
+  const float* input_h;                    /* device: water depth entering the step, row i at
+                                              input_h[i * input_h_stride] (data.x[:, -2]) */
+  int64_t input_h_stride;                  /* in elements */
+  const int64_t* node_bc;                  /* device [n_bc] ghost-cell rows (data.node_BC) */
+  const float* bc;                         /* device [n_bc] unit discharge of the step */
+  const float* edge_bc_length;             /* device [n_bc] */
+  int32_t n_bc;
+} msw_train_loss_desc;
+
+/* Doubles of the forward's scratch (4 per workgroup of launch 1, at least 4). */
+int msw_train_loss_workspace(const msw_train_loss_desc* desc, int64_t* scratch_doubles);
+/* pred, real: device [N][2] fp32.  loss_out: device float.  record_out: device double[12]. */
+int msw_train_loss_forward(const msw_train_loss_desc* desc, const float* pred, const float* real,
+                           double* scratch, float* loss_out, double* record_out, void* stream);
+/* record: the forward's, on the same desc, pred and real.  grad_out: device float (the gradient of
+ * the loss).  grad_pred: device [N][2], written.  grad_input_h: device [N] or NULL. */
+int msw_train_loss_backward(const msw_train_loss_desc* desc, const float* pred, const float* real,
+                            const double* record, const float* grad_out, float* grad_pred,
+                            float* grad_input_h, void* stream);
+/* Launch 1 of the forward for `total_rows` rows in all ranges together (from the code the launcher
+ * itself uses): workgroups (at most 512), rows a workgroup takes per round (256) and the rounds of
+ * its grid-stride loop, so that grid * rows_per_wg * iters >= total_rows; 0 rows: grid = iters = 0
+ * (the forward then skips launch 1).  MSW_ERR_INVALID: negative total_rows, a NULL output.  Host only.
+ * MSW_ERR_INVALID of the three functions above, before any HIP call: NULL desc or required pointer,
+ * num_ranges outside 1..64, a range with end < start, a negative start, an end past num_rows (or
+ * num_rows past the kernels' int32 row indices), ranges not ascending and disjoint, an unknown
+ * type_loss, num_graphs < 1, and with conservation != 0: NULL area or input_h, negative n_bc, or
+ * n_bc > 0 with a NULL node_bc, bc or edge_bc_length. */
+int msw_train_loss_launch(int64_t total_rows, int32_t* grid, int32_t* rows_per_wg, int32_t* iters);
+
 /* Diagnostics: route per-phase timestamps of wave 0 of workgroup 0 of every launch to the
  * device buffer `buf` (uint64[20]: {shader clock, 100 MHz clock} for phase marks 0..9).
  * Only builds compiled with -DMSW_TRACE record anything; NULL disables. */
 int msw_set_trace(msw_plan* plan, uint64_t* buf);
 
 /* sizeof() of a descriptor struct ("msw_linear", "msw_mlp", "msw_swegnn",
- * "msw_model_desc", "msw_graph_desc", "msw_plan_stats"); -1 if unknown.  Pure host code:
+ * "msw_model_desc", "msw_graph_desc", "msw_plan_stats", ..., "msw_train_loss_desc"); -1 if
+ * unknown.  Pure host code:
  * lets FFI bindings verify their struct layouts without a GPU. */
 int64_t msw_struct_size(const char* name);
 const char* msw_last_error(void);

@@ -1434,6 +1434,7 @@ int64_t msw_struct_size(const char* name) {
   if (!strcmp(name, "msw_mlp_grads")) return sizeof(msw_mlp_grads);
   if (!strcmp(name, "msw_flood_maps")) return sizeof(msw_flood_maps);
   if (!strcmp(name, "msw_zone_series")) return sizeof(msw_zone_series);
+  if (!strcmp(name, "msw_train_loss_desc")) return sizeof(msw_train_loss_desc);
   return -1;
 }
 

@@ -10,3 +10,6 @@ import os
 if os.environ.get("MSWEGNN_FUSED_ROLLOUT", "") not in ("", "0"):
     from mswegnn.hooks import install_fused_rollout
     install_fused_rollout()
+if os.environ.get("MSWEGNN_FUSED_LOSS", "") not in ("", "0"):
+    from mswegnn.hooks import install_fused_loss
+    install_fused_loss()

@@ -125,6 +125,22 @@ class MswZoneSeries(C.Structure):
                 ("h_max", C.c_void_p), ("q_max", C.c_void_p)]
 
 
+MAX_LOSS_RANGES = 64
+TRAIN_LOSS_RECORD = 12
+LOSS_TYPE = {"RMSE": 0, "MAE": 1}
+
+
+class MswTrainLossDesc(C.Structure):
+    _fields_ = [("num_rows", C.c_int64), ("num_ranges", C.c_int32), ("type_loss", C.c_int32),
+                ("ranges", (C.c_int64 * 2) * MAX_LOSS_RANGES),
+                ("only_where_water", C.c_int32), ("num_graphs", C.c_int32),
+                ("velocity_scaler", C.c_double), ("conservation", C.c_double),
+                ("seconds_per_step", C.c_double),
+                ("area", C.c_void_p), ("input_h", C.c_void_p), ("input_h_stride", C.c_int64),
+                ("node_bc", C.c_void_p), ("bc", C.c_void_p), ("edge_bc_length", C.c_void_p),
+                ("n_bc", C.c_int32)]
+
+
 # (name, restype, argtypes) of every entry point declared in include/mswegnn.h
 SYMBOLS = [
     ("msw_plan_create", C.c_int, [C.POINTER(MswGraphDesc), C.POINTER(MswModelDesc), C.c_int,
@@ -180,6 +196,12 @@ SYMBOLS = [
                                         C.c_void_p]),
     ("msw_mlp_train_backward", C.c_int, [C.POINTER(MswMlpTrainDesc), C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.POINTER(MswMlpGrads), C.c_void_p, C.c_void_p]),
+    ("msw_train_loss_workspace", C.c_int, [C.POINTER(MswTrainLossDesc), c_int64_p]),
+    ("msw_train_loss_forward", C.c_int, [C.POINTER(MswTrainLossDesc), C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("msw_train_loss_backward", C.c_int, [C.POINTER(MswTrainLossDesc), C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("msw_train_loss_launch", C.c_int, [C.c_int64, c_int32_p, c_int32_p, c_int32_p]),
 ]
 
 STRUCTS = {"msw_linear": MswLinear, "msw_mlp": MswMlp, "msw_swegnn": MswSwegnn,
@@ -187,7 +209,8 @@ STRUCTS = {"msw_linear": MswLinear, "msw_mlp": MswMlp, "msw_swegnn": MswSwegnn,
            "msw_plan_stats": MswPlanStats, "msw_exchange_desc": MswExchangeDesc,
            "msw_swegnn_train_desc": MswSwegnnTrainDesc, "msw_swegnn_grads": MswSwegnnGrads,
            "msw_mlp_train_desc": MswMlpTrainDesc, "msw_mlp_grads": MswMlpGrads,
-           "msw_flood_maps": MswFloodMaps, "msw_zone_series": MswZoneSeries}
+           "msw_flood_maps": MswFloodMaps, "msw_zone_series": MswZoneSeries,
+           "msw_train_loss_desc": MswTrainLossDesc}
 
 _lib = None
 

@@ -18,7 +18,9 @@ atomics, so the whole training forward / backward is deterministic.
 
 ``SWEGNN.forward``, the models' encoder / decoder calls and MSGNN's pooling (models/gnn.py of
 this package) route here on a GPU with autograd enabled; the scale selections, skip sums and
-the output mask stay elementwise torch ops.
+the output mask stay elementwise torch ops.  The loss that ``training_step`` evaluates on the
+model's output is built too: :mod:`mswegnn.loss` over ``msw_train_loss_*`` (csrc/loss.hip),
+opt-in through ``MSWEGNN_FUSED_LOSS=1``.
 """
 from __future__ import annotations
 

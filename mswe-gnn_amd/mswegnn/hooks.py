@@ -9,6 +9,13 @@ every step is one HIP ``msw_forward``.  ``install_fused_rollout()`` swaps that f
 call time, reach the fused path with no change to the callers.  ``models/__init__.py``
 calls it when ``MSWEGNN_FUSED_ROLLOUT=1``.  The reference's function stays available as
 ``training.train._reference_rollout_test``.
+
+``install_fused_loss()`` does the same for the name ``loss_function`` in ``training.train``
+(bound there by ``from training.loss import loss_function``; ``training_step``,
+train.py:125-145, looks it up at call time): it becomes :func:`mswegnn.loss.loss_function`,
+the HIP loss kernels on a GPU and an op-for-op torch composition elsewhere.
+``MSWEGNN_FUSED_LOSS=1`` installs it; the original stays as
+``training.train._reference_loss_function``.
 """
 import importlib.abc
 import sys
@@ -16,12 +23,20 @@ import sys
 TARGET = "training.train"
 
 
+WANTED = set()  # "rollout", "loss": what the installed hooks replace
+
+
 def _patch(mod):
-    from .rollout import rollout_test
-    if getattr(mod, "rollout_test", None) is rollout_test:
-        return
-    mod._reference_rollout_test = getattr(mod, "rollout_test", None)
-    mod.rollout_test = rollout_test
+    if "rollout" in WANTED:
+        from .rollout import rollout_test
+        if getattr(mod, "rollout_test", None) is not rollout_test:
+            mod._reference_rollout_test = getattr(mod, "rollout_test", None)
+            mod.rollout_test = rollout_test
+    if "loss" in WANTED:
+        from .loss import loss_function
+        if getattr(mod, "loss_function", None) is not loss_function:
+            mod._reference_loss_function = getattr(mod, "loss_function", None)
+            mod.loss_function = loss_function
 
 
 class _PatchingLoader(importlib.abc.Loader):
@@ -64,7 +79,20 @@ def install_fused_rollout():
     If ``training.train`` is itself being imported (it imports ``models`` through
     utils.miscellaneous before defining ``rollout_test``), the patch is applied by
     :func:`maybe_patch` at the first model call instead."""
+    _install("rollout")
+
+
+def install_fused_loss():
+    """Patch ``training.train.loss_function`` -- the name ``from training.loss import
+    loss_function`` bound there, which ``training_step`` looks up at call time -- with
+    :func:`mswegnn.loss.loss_function`, now if ``training.train`` is imported, else when it is
+    (mid-import: at the first model call, as for the rollout)."""
+    _install("loss")
+
+
+def _install(what):
     global PENDING
+    WANTED.add(what)
     mod = sys.modules.get(TARGET)
     if mod is not None:
         if _initializing(mod):

@@ -6,6 +6,13 @@ the all-torch autograd path of the same drop-in model on the same GPU.  Also rep
 and gradient agreement of the two paths at the first step.
 
     python tools/train_bench.py [--workload zenodo4] [--rollout-steps 4] [--steps 5] [--amp] [--fp64-ref]
+                                [--loss bench|reference|fused]
+
+--loss bench (the default) times ``rmse_loss`` below: only_where_water=False, velocity_scaler=1.
+``reference`` is config.yaml's trainer_options (RMSE, only_where_water=True, velocity_scaler=7,
+conservation=0) through the torch composition of mswegnn/loss.py -- its boolean-mask selection
+reads the device once per rollout step -- and ``fused`` the same options through the HIP loss
+kernels (csrc/loss.hip).
 """
 import argparse
 import json
@@ -41,6 +48,8 @@ def main():
                     help="also the first-step gradients of the torch path in float64 (the yardstick)")
     ap.add_argument("--amp", action="store_true",
                     help="also both paths under main.py's precision='16-mixed' (autocast fp16 + GradScaler)")
+    ap.add_argument("--loss", choices=["bench", "reference", "fused"], default="bench",
+                    help="the per-step loss: rmse_loss (default), config.yaml's options in torch, or the HIP loss")
     ap.add_argument("--parts", default="swegnn,mlp,pool",
                     help="diagnostics: which layer kinds run on the HIP training kernels")
     a = ap.parse_args()
@@ -63,6 +72,14 @@ def main():
     with torch.no_grad():  # a target the model does not already reproduce (well-conditioned RMSE)
         y = (m0.rollout(g, R) * 1.1 + 0.01).detach()
     state0 = {k: v.detach().clone() for k, v in m0.state_dict().items()}
+    from mswegnn.loss import loss_function, torch_loss_function
+    CONFIG = dict(type_loss="RMSE", only_where_water=True, conservation=0, velocity_scaler=7)  # config.yaml
+
+    def step_loss(preds, temp, target, i):
+        if a.loss == "bench":
+            return rmse_loss(preds, target[:, :, i], n0)
+        fn = loss_function if a.loss == "fused" else torch_loss_function
+        return fn(preds, target[:, :, i], temp, temp.BC[:, -2:, i + 1].mean(1), **CONFIG)
 
     def run(engine, amp=False):
         """Training steps of one path; amp: main.py's precision='16-mixed' (autocast fp16 around
@@ -86,7 +103,7 @@ def main():
                                                                 type_BC=temp.type_BC)
                     preds = m(temp)
                     temp.x = use_prediction(temp.x, preds, m.previous_t)
-                    losses.append(rmse_loss(preds, y[:, :, i], n0))
+                    losses.append(step_loss(preds, temp, y, i))
                 loss = torch.stack(losses).mean()
             scaler.scale(loss).backward()
             scaler.unscale_(opt)
@@ -111,7 +128,8 @@ def main():
         return (time.perf_counter() - t0) / max(a.steps, 1), float(first.detach()), grads
     if a.only:
         t, l, _ = run("auto" if a.only == "hip" else "torch")
-        print(json.dumps({"only": a.only, "ms_per_training_step": t * 1e3, "first_loss": l}), flush=True)
+        print(json.dumps({"only": a.only, "ms_per_training_step": t * 1e3, "first_loss": l,
+                          **({} if a.loss == "bench" else {"loss": a.loss})}), flush=True)
         return
     t_hip, l_hip, g_hip = run("auto")
     t_torch, l_torch, g_torch = run("torch")
@@ -144,7 +162,7 @@ def main():
                                                         type_BC=temp.type_BC)
             preds = m64(temp)
             temp.x = use_prediction(temp.x, preds, m64.previous_t)
-            losses.append(rmse_loss(preds, y64[:, :, i], n0))
+            losses.append(step_loss(preds, temp, y64, i))
         torch.stack(losses).mean().backward()
         torch.nn.utils.clip_grad_norm_(m64.parameters(), 1.0)
         g64s = {n: p.grad.detach().float() for n, p in m64.named_parameters() if p.grad is not None}
@@ -166,7 +184,8 @@ def main():
             amp["torch_amp_vs_fp64_global_rel"] = global_rel(g_torch_amp, g64s)
     pt = per_tensor(g_hip, g_torch)
     worst_k = max(pt, key=pt.get)
-    print(json.dumps({"workload": a.workload, "fine_nodes": n0, "all_nodes": desc["all_nodes"],
+    print(json.dumps({"workload": a.workload, **({} if a.loss == "bench" else {"loss": a.loss}),
+                      "fine_nodes": n0, "all_nodes": desc["all_nodes"],
                       "rollout_steps_per_training_step": R, "hip_parts": sorted(parts),
                       "hip_ms_per_training_step": t_hip * 1e3, "torch_ms_per_training_step": t_torch * 1e3,
                       "speedup": t_torch / t_hip,
