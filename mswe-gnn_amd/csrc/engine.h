@@ -326,7 +326,7 @@ hipError_t launch_copy_rows(const float* src, const int* srows, float* dst, cons
                             hipStream_t st);
 
 // What one launch runs: the kernel instantiation, its grid and workgroup, chosen from the
-// launch's arguments by pick_* (kernels/k_pick.h).  The launchers launch exactly this and
+// launch's arguments by pick_* (kernels/k_pick.h).  launch_pick launches exactly this and
 // msw_plan_schedule prints it, so the description cannot drift from the launch.
 struct Pick {
   const void* fn;   // the kernel (null with err = 0: nothing to launch)
@@ -340,6 +340,56 @@ struct Pick {
   int per_wg;       // units one workgroup takes per round
 };
 
+static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+
+// one tile per wave while that grid is resident at once; grid-stride loop beyond that
+template <class A>
+static inline bool tile_loop(const A& a) {
+  return a.fit_blocks > 0 && a.max_blocks > 0 && cdiv(a.ntiles, kWaves) > a.fit_blocks;
+}
+
+// XCD packing of a one-round grid of g workgroups (b: the launch's argument copy): the
+// fewest XCDs (1, 2, 4 <= c.xcd_max) that hold one workgroup per CU, else all eight
+template <class A>
+static inline dim3 xcd_grid(A& b, long g) {
+  b.c.xcd = 0;
+  for (int k = 1; k <= b.c.xcd_max && k < kXcds; k *= 2)
+    if (g <= (long)kCusPerXcd * k) {
+      b.c.xcd = k;
+      return dim3((unsigned)(cdiv(g, k) * kXcds));
+    }
+  return dim3((unsigned)g);
+}
+
+// Launches exactly what was picked.
+template <class A>
+static inline hipError_t launch_pick(const Pick& p, const A& a, hipStream_t st) {
+  if (p.err) return (hipError_t)p.err;
+  if (!p.fn) return hipSuccess;  // nothing to do
+  A b = a;
+  const dim3 grid = p.pack ? xcd_grid(b, p.grid) : dim3((unsigned)p.grid);
+  if (!p.pack) b.c.xcd = 0;
+  void* args[] = {&b};
+  return hipLaunchKernel(p.fn, grid, dim3(64 * p.waves), args, p.lds, st);
+}
+
+// Names one kernel instantiation of a width: the family and the flags that choose among its
+// template arguments (a family ignores the flags it does not take).  variant_of<NT>
+// (kernels/k_pick.h) maps a key to the kernel, its workgroup and its dynamic-LDS rule; the
+// picks, the residency queries and prepare_kernels all go through it.
+enum Family { K_ENCODE, K_ENCODE_COOP, K_EDGE_HOP, K_EDGE_COOP, K_EDGE_MLP, K_HOP, K_HOP_ROWS, K_HOP_SPLIT,
+              K_HOP_COOP, K_POOL_ROWS, K_POOL_EDGE, K_EPI, K_DECODE, K_FAMILIES };
+struct VariantKey {
+  int family;
+  int prelu = 0;   // every MLP activation is PReLU (Common::prelu)
+  int last = 0;    // last hop of the layer (with the epilogue)
+  int loop = 0;    // grid-stride
+  int waves = 0;   // waves per tile of the cooperative kernels (pool_edge: 0 / 1 = one)
+  int fuse = 0;    // edge_coop: 1 pooling, 2 unpooling fused in
+  int dec = 0;     // encoders: the previous step's decoder runs first
+  int stream = 0;  // encode: streaming stores
+};
+
 // NT = Fp / 16 feature tiles (row width Fp = 16, 32, 64 -> NT = 1, 2, 4; hid_features 33..63: Fp = 64)
 template <int NT> Pick pick_encode(const EncodeArgs& a);
 template <int NT> Pick pick_edge_hop(const EdgeHopArgs& a);
@@ -349,16 +399,8 @@ template <int NT> Pick pick_pool(const PoolArgs& a);
 template <int NT> Pick pick_epi(const EpiArgs& a);
 template <int NT> Pick pick_decode(const DecodeArgs& a);
 template <int NT> hipError_t prepare_kernels();
-// kind 0 encode, 1 edge_hop, 2 hop, 3 pool, 5 pool edge tiles, 6 row epilogue (and the
-// cooperative / split / row-layout variants, kernels_impl.h kernel_of)
-template <int NT> int resident_blocks(int kind, int prelu, int last, size_t dyn_bytes, int loop);
-template <int NT> hipError_t launch_encode(const EncodeArgs& a, hipStream_t st);
-template <int NT> hipError_t launch_edge_hop(const EdgeHopArgs& a, hipStream_t st);
-template <int NT> hipError_t launch_edge_mlp(const EdgeHopArgs& a, hipStream_t st);
-template <int NT> hipError_t launch_hop(const HopArgs& a, hipStream_t st);
-template <int NT> hipError_t launch_pool(const PoolArgs& a, hipStream_t st);
-template <int NT> hipError_t launch_epi(const EpiArgs& a, hipStream_t st);
+// workgroups of variant k the whole chip holds at once, with a weight region of `floats`
+template <int NT> int resident_blocks(const VariantKey& k, int floats);
 template <int NT> hipError_t launch_rowmlp(const RowMlpArgs& a, hipStream_t st);
-template <int NT> hipError_t launch_decode(const DecodeArgs& a, hipStream_t st);
 
 }  // namespace msw

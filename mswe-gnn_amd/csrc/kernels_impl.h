@@ -20,6 +20,7 @@
 #pragma once
 #include <cstdio>
 #include <initializer_list>
+#include <set>
 #include <type_traits>
 #include <utility>
 

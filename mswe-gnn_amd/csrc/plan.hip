@@ -19,6 +19,7 @@
 #include <memory>
 #include <numeric>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/mswegnn.h"
@@ -155,12 +156,18 @@ int upload(T** p, const std::vector<T>& v, int64_t& counter) {
   return MSW_OK;
 }
 
-hipError_t rowmlp_dispatch(int NT, const RowMlpArgs& ra, hipStream_t st = nullptr) {
+// The one dispatch on a plan's width: f(std::integral_constant<int, NT>) for NT = 1, 2, 4.
+template <class F>
+auto with_nt(int NT, F&& f) {
   switch (NT) {
-    case 1: return launch_rowmlp<1>(ra, st);
-    case 2: return launch_rowmlp<2>(ra, st);
-    default: return launch_rowmlp<4>(ra, st);
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    default: return f(std::integral_constant<int, 4>{});
   }
+}
+
+hipError_t rowmlp_dispatch(int NT, const RowMlpArgs& ra, hipStream_t st = nullptr) {
+  return with_nt(NT, [&](auto nt) { return launch_rowmlp<nt>(ra, st); });
 }
 
 }  // namespace
@@ -272,17 +279,25 @@ struct Launch {
     DecodeArgs dec;
   };
   Launch() { memset((void*)this, 0, sizeof(*this)); }
-  Common& common() {
-    switch (kind) {
-      case L_ENCODE: return enc.c;
+  // f(the argument struct of this launch's kind)
+  template <class L, class F>
+  static decltype(auto) visit(L& l, F&& f) {
+    switch (l.kind) {
+      case L_ENCODE: return f(l.enc);
       case L_EDGE_HOP:
-      case L_EDGE_MLP: return eh.c;
-      case L_HOP: return hop.c;
-      case L_EXCHANGE: return xch.c;
-      case L_EPI: return ep.c;
-      case L_DECODE: return dec.c;
-      default: return pool.c;
+      case L_EDGE_MLP: return f(l.eh);
+      case L_HOP: return f(l.hop);
+      case L_EXCHANGE: return f(l.xch);
+      case L_EPI: return f(l.ep);
+      case L_DECODE: return f(l.dec);
+      default: return f(l.pool);
     }
+  }
+  Common& common() {
+    return visit(*this, [](auto& a) -> Common& { return a.c; });
+  }
+  const Common& common() const {
+    return visit(*this, [](const auto& a) -> const Common& { return a.c; });
   }
 };
 
@@ -1039,19 +1054,22 @@ int relocate(msw_plan* P, std::vector<Launch>& q, bool mlp_only = false) {
 // Grid cap of a grid-stride launch: the workgroups the chip holds at once, so that each
 // stages its weight region once (large meshes) and none waits for a second wave of blocks.
 // MSW_GRID_CAP=n (tests): at most n; 0 (the occupancy query failed) stays 0.
-int resident_of(const msw_plan* P, int kind, int prelu, int last, size_t bytes, int loop) {
-  int r;
-  switch (P->NT) {
-    case 1: r = resident_blocks<1>(kind, prelu, last, bytes, loop); break;
-    case 2: r = resident_blocks<2>(kind, prelu, last, bytes, loop); break;
-    default: r = resident_blocks<4>(kind, prelu, last, bytes, loop); break;
-  }
+// The keys below are deliberate carry-overs where they name another instantiation than the one
+// launched (the encoder asks about the non-decoding, non-streaming k_encode; a cooperative
+// edge hop with fused (un)pooling about the unfused kernel; the row-layout hop has no region;
+// a middle hop asks with its layer's region though it stages none): another key could move a
+// size threshold.
+int resident_of(const msw_plan* P, const VariantKey& k, int floats) {
+  const int r = with_nt(P->NT, [&](auto nt) { return resident_blocks<nt>(k, floats); });
   return P->kn.grid_cap > 0 ? std::min(r, P->kn.grid_cap) : r;
 }
+// max_blocks / fit_blocks: the grid-stride and the one-tile-per-wave variant of key k
 template <class A>
-void caps(msw_plan* P, A& a, int kind, int prelu, int last, int floats) {
-  a.max_blocks = resident_of(P, kind, prelu, last, (size_t)floats * 4, 1);
-  a.fit_blocks = resident_of(P, kind, prelu, last, (size_t)floats * 4, 0);
+void caps(const msw_plan* P, A& a, VariantKey k, int floats) {
+  k.loop = 1;
+  a.max_blocks = resident_of(P, k, floats);
+  k.loop = 0;
+  a.fit_blocks = resident_of(P, k, floats);
 }
 constexpr int kHopLoopTiles = 65536;
 // middle hops of scales with at least this many edge tiles run in the row layout
@@ -1060,139 +1078,131 @@ constexpr int kRowHopMinTiles = kHopLoopTiles;
 // MSW_HOP_ROWS=2: every middle hop in the row layout, at any size (parity tests)
 bool row_hops_forced(const msw_plan* P) { return P->kn.hop_rows == 2; }
 constexpr long kEncCoopWaves = 4096;
-void set_grid_cap(msw_plan* P, Launch& L) {
+// set_grid_cap, one function per launch kind: the residency figures of a launch and the
+// variant choices that go by them (cooperative / split / row-layout / streaming / direct)
+void cap_encode(const msw_plan* P, EncodeArgs& a) {
+  a.max_blocks = resident_of(P, {K_ENCODE, a.c.prelu}, a.lds_floats);
+  // F = 64: four waves per row tile while that leaves <= 4 waves per SIMD (k_encode_coop;
+  // zenodo4_f64 +5.0 %; at F = 32 the halved chains are too short for the seven LDS
+  // exchanges: -2.5 %; MSW_ENC_COOP=0/1 overrides)
+  bool coop = P->NT == 4 && (long)(a.Npad / kRowsPerWave) * P->NT <= kEncCoopWaves;
+  if (P->kn.enc_coop >= 0) coop = P->NT >= 2 && P->kn.enc_coop != 0;
+  a.coop = coop ? P->NT : 0;
+  // grid-stride (more 64-row chunks than resident workgroups) without the decoder: the
+  // encoder's rows (config 5: 1.26 GB per launch) go out as streaming stores
+  a.stream = !a.coop && !a.dec.on && a.max_blocks > 0 && a.Npad / kRowsPerBlock > a.max_blocks;
+}
+void cap_edge_mlp(const msw_plan* P, EdgeHopArgs& a) {
+  // k_edge_mlp: two waves per SIMD, one chunk each.  (A software-pipelined variant, one wave
+  // per SIMD walking ~2 chunks with the next chunk's gathers in flight, spilled once the
+  // operands were LDS-typed and lost: zenodo4_f64 27.76 / 27.91 vs 28.08 / 28.09 M,
+  // profiles/r04/ab_f64_lds_operands.txt; removed in round 6.)  Waves 4..7 start 2 x 2 k
+  // cycles late (k_edge_mlp 22.0 -> 21.2 us, profiles/r05/ab_f64_mlp_stagger.txt).
+  a.stagger = kMlpStagger;
+  a.max_blocks = resident_of(P, {K_EDGE_MLP, a.c.prelu}, a.reg.len);
+}
+void cap_edge_hop(const msw_plan* P, EdgeHopArgs& a) {
+  // the grid-stride variant stages the whole region, one tile per wave keeps the filter in registers
+  a.max_blocks = resident_of(P, {K_EDGE_HOP, a.c.prelu, a.last, 1}, a.reg.len);
+  a.fit_blocks = resident_of(P, {K_EDGE_HOP, a.c.prelu, a.last, 0}, a.reg_nf);
+  // MSW_EH_LOOP=1: the grid-stride variant at any size (parity tests of the large-mesh path)
+  if (P->kn.eh_loop && a.max_blocks > 0 && a.ntiles > kWaves) a.fit_blocks = 1;
+  // two waves per tile (k_edge_coop) while the tiles leave most SIMDs idle: one tile
+  // per wave at most, no grid-stride loop, an epilogue of projections only
+  const bool loop = tile_loop(a);
+  const bool epi_ok = !a.last || (!a.epi.dec.on && a.epi.uu_a < 0);
+  // ... and its grid resident at once (a second round of workgroups costs more than the
+  // halved MLP chain saves: measured +4.7 us on the finest unpooling of zenodo4)
+  // (F = 32: two waves per tile; F = 64: four, one tile per workgroup)
+  const int pw = P->NT == 2 ? 2 : P->NT == 4 ? 4 : 0;
+  const int coop_fit = pw ? resident_of(P, {K_EDGE_COOP, a.c.prelu, a.last, 0, pw}, a.reg_nf) : 0;
+  a.coop = (pw && !loop && epi_ok && P->coop_waves > 0 && (long)pw * a.ntiles <= P->coop_waves &&
+            (pw * a.ntiles + kWaves - 1) / kWaves <= coop_fit) ? pw : 0;
+  // F = 64 where four waves per tile do not fit one round: two, two tiles per workgroup
+  // (zenodo4_f64 scale 1: 508 tiles in one round, +2.0 %; MSW_COOP2_F64=0 off, =2 also in
+  // place of four, for tests)
+  // fused pooling exists in the cooperative kernels only (pool_fusable): F = 32 two waves
+  // per tile; F = 64 four, or two where four do not fit one round (below)
+  if ((a.pool.slots || a.pool.parent) && P->NT == 2) a.coop = 2;
+  const int c2 = P->kn.coop2_f64;
+  if (c2 == 2 && a.coop == 4) a.coop = 0;
+  a.wdirect = 0;
+  if (P->NT == 4 && !a.coop && !loop && epi_ok && P->coop_waves > 0 && 2L * a.ntiles <= P->coop_waves && c2) {
+    const int need = (2 * a.ntiles + kWaves - 1) / kWaves;
+    const int wd = P->kn.coop2_direct;
+    const VariantKey two{K_EDGE_COOP, a.c.prelu, a.last, 0, 2};
+    if (need <= resident_of(P, two, a.reg_nf)) {
+      a.coop = 2;
+      a.wdirect = wd == 2 && a.reg.len > 0;
+    } else if (wd != 0 && a.reg.len > 0 && need <= resident_of(P, two, 0)) {
+      // the staged MLP region (96 KB) holds one workgroup per CU: read it from its blob
+      // copy instead, two workgroups per CU, and the grid fits one round (the finest
+      // unpooling of zenodo4_f64: 652 tiles; MSW_COOP2_DIRECT=0 off)
+      a.coop = 2;
+      a.wdirect = 1;
+    }
+  }
+  if ((a.pool.slots || a.pool.parent) && !a.coop) a.coop = 2;  // F = 64 fused: two waves per tile, any grid
+}
+void cap_hop(const msw_plan* P, HopArgs& h) {
+  caps(P, h, {K_HOP, h.c.prelu, h.last}, h.reg.len);
+  // one tile per wave below kHopLoopTiles: the grid-stride variant measured 1.1-1.6 % slower on the batch of 8 and
+  // dk15, equal on the 1M-node mesh whose finest hop alone it runs 3 % faster
+  // (profiles/r01_v7/ab_edge_waves.txt)
+  // (waived under MSW_GRID_CAP, whose point is the grid-stride variant on a small mesh)
+  if (h.ntiles < kHopLoopTiles && P->kn.grid_cap <= 0) h.max_blocks = 0;
+  {  // F = 64: feature-split middle hops below the grid-stride size (k_hop_split;
+     // zenodo4_f64 +4.6 %, F = 32 neutral; MSW_HOP_SPLIT=0/1 overrides the rule)
+    bool sp = P->NT == 4 && h.max_blocks == 0;
+    if (P->kn.hop_split >= 0) sp = P->kn.hop_split != 0;
+    h.split = (sp && P->NT >= 2 && !h.last) ? 1 : 0;
+  }
+  // row layout for the grid-stride middle hops of large scales (k_hop_rows)
+  h.rows = 0;
+  if (P->kn.hop_rows != 0 && !h.last && (tile_loop(h) || row_hops_forced(P)) && h.rptr && h.redge) {
+    h.rows = 1;
+    h.split = 0;
+    h.max_blocks = resident_of(P, {K_HOP_ROWS}, 0);
+  }
+  // a last hop with an epilogue on few tiles: P = F / 16 waves per tile (k_hop_coop)
+  const int pw = P->NT >= 2 ? P->NT : 0;
+  h.coop = 0;
+  if (h.last && pw && !tile_loop(h) && P->coop_waves > 0 && (long)pw * h.ntiles <= P->coop_waves &&
+      (pw * h.ntiles + kWaves - 1) / kWaves <= resident_of(P, {K_HOP_COOP, h.c.prelu, 1, 0, pw}, h.reg.len))
+    h.coop = pw;
+}
+void cap_pool(const msw_plan* P, PoolArgs& a) {
+  // edge tiles while they all fit on the chip at once (latency-bound launch), else rows
+  const int fe = resident_of(P, {K_POOL_EDGE}, a.reg.len);
+  a.rows = !(fe > 0 && (a.etiles + kWaves - 1) / kWaves <= fe);
+  a.ntiles = a.rows ? a.rtiles : a.etiles;
+  caps(P, a, {K_POOL_ROWS}, a.reg.len);
+  // two waves per edge tile (projection split) while that grid too is resident at once
+  // (F = 32: two waves per tile, F = 64: four)
+  const int pw = P->NT >= 2 ? P->NT : 0;
+  a.coop = (!a.rows && pw && P->coop_waves > 0 && (long)pw * a.etiles <= P->coop_waves &&
+            (pw * a.etiles + kWaves - 1) / kWaves <= fe) ? pw : 0;
+  // 2F-wide first edge-MLP layer: 2 * F / 16 waves per tile (one U and one V output tile
+  // each) while resident (zenodo4_f64 +1.8 %, zenodo4 +0.6 %, profiles/r02_s4/ab_pool_p8.txt,
+  // ab_pool_wide_f32.txt); MSW_POOL_WIDE=0: F / 16 waves; bit-identical either way
+  const bool wide = P->kn.pool_wide != 0;
+  if (wide && pw && a.coop == pw && a.np.h1t == 2 * pw) {
+    const int f8 = resident_of(P, {K_POOL_EDGE, 0, 0, 0, 2 * pw}, a.reg.len);
+    if (f8 > 0 && a.etiles <= f8) a.coop = 2 * pw;
+  }
+}
+void set_grid_cap(const msw_plan* P, Launch& L) {
   // XCD packing (Common::xcd_max) applies to the hop, edge-hop, pooling and row-epilogue
   // launches (the only one-round grids small enough to fit one XCD)
   if (L.kind != L_HOP && L.kind != L_EDGE_HOP && L.kind != L_POOL && L.kind != L_EPI) L.common().xcd_max = 0;
   switch (L.kind) {
-    case L_ENCODE: {
-      L.enc.max_blocks = resident_of(P, 0, L.enc.c.prelu, 0, (size_t)L.enc.lds_floats * 4, 0);
-      // F = 64: four waves per row tile while that leaves <= 4 waves per SIMD (k_encode_coop;
-      // zenodo4_f64 +5.0 %; at F = 32 the halved chains are too short for the seven LDS
-      // exchanges: -2.5 %; MSW_ENC_COOP=0/1 overrides)
-      bool coop = P->NT == 4 && (long)(L.enc.Npad / kRowsPerWave) * P->NT <= kEncCoopWaves;
-      if (P->kn.enc_coop >= 0) coop = P->NT >= 2 && P->kn.enc_coop != 0;
-      L.enc.coop = coop ? P->NT : 0;
-      // grid-stride (more 64-row chunks than resident workgroups) without the decoder: the
-      // encoder's rows (config 5: 1.26 GB per launch) go out as streaming stores
-      L.enc.stream = !L.enc.coop && !L.enc.dec.on && L.enc.max_blocks > 0 &&
-                     L.enc.Npad / kRowsPerBlock > L.enc.max_blocks;
-      break;
-    }
-    case L_EDGE_MLP: {
-      // k_edge_mlp: two waves per SIMD, one chunk each.  (A software-pipelined variant, one wave
-      // per SIMD walking ~2 chunks with the next chunk's gathers in flight, spilled once the
-      // operands were LDS-typed and lost: zenodo4_f64 27.76 / 27.91 vs 28.08 / 28.09 M,
-      // profiles/r04/ab_f64_lds_operands.txt; removed in round 6.)  Waves 4..7 start 2 x 2 k
-      // cycles late (k_edge_mlp 22.0 -> 21.2 us, profiles/r05/ab_f64_mlp_stagger.txt).
-      L.eh.stagger = kMlpStagger;
-      L.eh.max_blocks = resident_of(P, 10, L.eh.c.prelu, 0, (size_t)L.eh.reg.len * 4, 1);
-      break;
-    }
-    case L_EDGE_HOP: {
-      EdgeHopArgs& a = L.eh;
-      caps(P, a, 1, a.c.prelu, a.last, a.reg.len);
-      a.fit_blocks = resident_of(P, 1, a.c.prelu, a.last, (size_t)a.reg_nf * 4, 0);
-      // MSW_EH_LOOP=1: the grid-stride variant at any size (parity tests of the large-mesh path)
-      if (P->kn.eh_loop && a.max_blocks > 0 && a.ntiles > kWaves) a.fit_blocks = 1;
-      // two waves per tile (k_edge_coop) while the tiles leave most SIMDs idle: one tile
-      // per wave at most, no grid-stride loop, an epilogue of projections only
-      const bool loop = a.fit_blocks > 0 && a.max_blocks > 0 && (a.ntiles + kWaves - 1) / kWaves > a.fit_blocks;
-      const bool epi_ok = !a.last || (!a.epi.dec.on && a.epi.uu_a < 0);
-      // ... and its grid resident at once (a second round of workgroups costs more than the
-      // halved MLP chain saves: measured +4.7 us on the finest unpooling of zenodo4)
-      // (F = 32: two waves per tile; F = 64: four, one tile per workgroup)
-      const int pw = P->NT == 2 ? 2 : P->NT == 4 ? 4 : 0;
-      const int coop_fit = pw ? resident_of(P, 7, a.c.prelu, a.last, (size_t)a.reg_nf * 4, 0) : 0;
-      a.coop = (pw && !loop && epi_ok && P->coop_waves > 0 && (long)pw * a.ntiles <= P->coop_waves &&
-                (pw * a.ntiles + kWaves - 1) / kWaves <= coop_fit) ? pw : 0;
-      // F = 64 where four waves per tile do not fit one round: two, two tiles per workgroup
-      // (zenodo4_f64 scale 1: 508 tiles in one round, +2.0 %; MSW_COOP2_F64=0 off, =2 also in
-      // place of four, for tests)
-      // fused pooling exists in the cooperative kernels only (pool_fusable): F = 32 two waves
-      // per tile; F = 64 four, or two where four do not fit one round (below)
-      if ((a.pool.slots || a.pool.parent) && P->NT == 2) a.coop = 2;
-      const int c2 = P->kn.coop2_f64;
-      if (c2 == 2 && a.coop == 4) a.coop = 0;
-      a.wdirect = 0;
-      if (P->NT == 4 && !a.coop && !loop && epi_ok && P->coop_waves > 0 && 2L * a.ntiles <= P->coop_waves && c2) {
-        const int need = (2 * a.ntiles + kWaves - 1) / kWaves;
-        const int wd = P->kn.coop2_direct;
-        if (need <= resident_of(P, 12, a.c.prelu, a.last, (size_t)a.reg_nf * 4, 0)) {
-          a.coop = 2;
-          a.wdirect = wd == 2 && a.reg.len > 0;
-        } else if (wd != 0 && a.reg.len > 0 && need <= resident_of(P, 12, a.c.prelu, a.last, 0, 0)) {
-          // the staged MLP region (96 KB) holds one workgroup per CU: read it from its blob
-          // copy instead, two workgroups per CU, and the grid fits one round (the finest
-          // unpooling of zenodo4_f64: 652 tiles; MSW_COOP2_DIRECT=0 off)
-          a.coop = 2;
-          a.wdirect = 1;
-        }
-      }
-      if ((a.pool.slots || a.pool.parent) && !a.coop) a.coop = 2;  // F = 64 fused: two waves per tile, any grid
-      break;
-    }
-    case L_HOP:
-      caps(P, L.hop, 2, L.hop.c.prelu, L.hop.last, L.hop.reg.len);
-      // one tile per wave below kHopLoopTiles: the grid-stride variant measured 1.1-1.6 % slower on the batch of 8 and
-      // dk15, equal on the 1M-node mesh whose finest hop alone it runs 3 % faster
-      // (profiles/r01_v7/ab_edge_waves.txt)
-      // (waived under MSW_GRID_CAP, whose point is the grid-stride variant on a small mesh)
-      if (L.hop.ntiles < kHopLoopTiles && P->kn.grid_cap <= 0) L.hop.max_blocks = 0;
-      {  // F = 64: feature-split middle hops below the grid-stride size (k_hop_split;
-         // zenodo4_f64 +4.6 %, F = 32 neutral; MSW_HOP_SPLIT=0/1 overrides the rule)
-        bool sp = P->NT == 4 && L.hop.max_blocks == 0;
-        if (P->kn.hop_split >= 0) sp = P->kn.hop_split != 0;
-        L.hop.split = (sp && P->NT >= 2 && !L.hop.last) ? 1 : 0;
-      }
-      {  // row layout for the grid-stride middle hops of large scales (k_hop_rows)
-        HopArgs& h = L.hop;
-        const bool loop = h.fit_blocks > 0 && h.max_blocks > 0 && (h.ntiles + kWaves - 1) / kWaves > h.fit_blocks;
-        const bool want = P->kn.hop_rows != 0;
-        h.rows = 0;
-        if (want && !h.last && (loop || row_hops_forced(P)) && h.rptr && h.redge) {
-          h.rows = 1;
-          h.split = 0;
-          h.max_blocks = resident_of(P, 14, 0, 0, 0, 1);
-        }
-      }
-      {  // a last hop with an epilogue on few tiles: P = F / 16 waves per tile (k_hop_coop)
-        HopArgs& h = L.hop;
-        const bool loop = h.fit_blocks > 0 && h.max_blocks > 0 && (h.ntiles + kWaves - 1) / kWaves > h.fit_blocks;
-        const int pw = P->NT >= 2 ? P->NT : 0;
-        h.coop = 0;
-        if (h.last && pw && !loop && P->coop_waves > 0 && (long)pw * h.ntiles <= P->coop_waves &&
-            (pw * h.ntiles + kWaves - 1) / kWaves <= resident_of(P, 9, h.c.prelu, 1, (size_t)h.reg.len * 4, 0))
-          h.coop = pw;
-      }
-      break;
-    case L_EXCHANGE: break;
-    case L_DECODE: break;
-    case L_EPI:
-      caps(P, L.ep, 6, L.ep.c.prelu, 1, L.ep.reg.len);
-      break;
-    default: {
-      // edge tiles while they all fit on the chip at once (latency-bound launch), else rows
-      PoolArgs& a = L.pool;
-      const int fe = resident_of(P, 5, 0, 0, (size_t)a.reg.len * 4, 0);
-      a.rows = !(fe > 0 && (a.etiles + kWaves - 1) / kWaves <= fe);
-      a.ntiles = a.rows ? a.rtiles : a.etiles;
-      caps(P, a, 3, 0, 0, a.reg.len);
-      // two waves per edge tile (projection split) while that grid too is resident at once
-      // (F = 32: two waves per tile, F = 64: four)
-      const int pw = P->NT >= 2 ? P->NT : 0;
-      a.coop = (!a.rows && pw && P->coop_waves > 0 && (long)pw * a.etiles <= P->coop_waves &&
-                (pw * a.etiles + kWaves - 1) / kWaves <= fe) ? pw : 0;
-      // 2F-wide first edge-MLP layer: 2 * F / 16 waves per tile (one U and one V output tile
-      // each) while resident (zenodo4_f64 +1.8 %, zenodo4 +0.6 %, profiles/r02_s4/ab_pool_p8.txt,
-      // ab_pool_wide_f32.txt); MSW_POOL_WIDE=0: F / 16 waves; bit-identical either way
-      const bool wide = P->kn.pool_wide != 0;
-      if (wide && pw && a.coop == pw && a.np.h1t == 2 * pw) {
-        const int f8 = resident_of(P, 13, 0, 0, (size_t)a.reg.len * 4, 0);
-        if (f8 > 0 && a.etiles <= f8) a.coop = 2 * pw;
-      }
-      break;
-    }
+    case L_ENCODE: return cap_encode(P, L.enc);
+    case L_EDGE_MLP: return cap_edge_mlp(P, L.eh);
+    case L_EDGE_HOP: return cap_edge_hop(P, L.eh);
+    case L_HOP: return cap_hop(P, L.hop);
+    case L_EPI: return caps(P, L.ep, {K_EPI, L.ep.c.prelu, 1}, L.ep.reg.len);
+    case L_POOL: return cap_pool(P, L.pool);
+    default: return;  // exchanges and the forward decoder have no grid to cap
   }
 }
 
@@ -1203,27 +1213,13 @@ const Launch* lds_overflow(const msw_plan* P) {
     for (const Launch& L : *q) {
       if (L.kind != L_EDGE_HOP || !(L.eh.coop == 2 || L.eh.coop == 4) || L.eh.wdirect) continue;
       const int fuse = L.eh.pool.slots ? 1 : L.eh.pool.parent ? 2 : 0;
-      const int cap = P->NT == 4 ? edge_coop_lds_cap<4>(L.eh.coop, fuse) : edge_coop_lds_cap<2>(2, fuse);
+      const int cap = with_nt(P->NT, [&](auto nt) { return edge_coop_lds_cap<nt>(L.eh.coop, fuse); });
       if (eh_lds_bytes(L.eh.reg_nf) > (size_t)cap) return &L;
     }
   return nullptr;
 }
 
-template <int NT>
-hipError_t launch_one(const Launch& L, hipStream_t st) {
-  switch (L.kind) {
-    case L_ENCODE: return launch_encode<NT>(L.enc, st);
-    case L_EDGE_HOP: return launch_edge_hop<NT>(L.eh, st);
-    case L_EDGE_MLP: return launch_edge_mlp<NT>(L.eh, st);
-    case L_HOP: return launch_hop<NT>(L.hop, st);
-    case L_POOL: return launch_pool<NT>(L.pool, st);
-    case L_EPI: return launch_epi<NT>(L.ep, st);
-    case L_DECODE: return launch_decode<NT>(L.dec, st);
-    default: return hipErrorInvalidValue;  // exchanges are run by run_schedule / the group driver
-  }
-}
-
-// What launch_one would launch (engine.h Pick): the launchers run these same pick_* functions.
+// What launch_one launches (engine.h Pick), and msw_plan_schedule prints.
 template <int NT>
 Pick pick_one(const Launch& L) {
   switch (L.kind) {
@@ -1236,6 +1232,13 @@ Pick pick_one(const Launch& L) {
     case L_DECODE: return pick_decode<NT>(L.dec);
     default: return Pick{};
   }
+}
+Pick pick_one(const msw_plan* P, const Launch& L) {
+  return with_nt(P->NT, [&](auto nt) { return pick_one<nt>(L); });
+}
+hipError_t launch_one(const msw_plan* P, const Launch& L, hipStream_t st) {
+  if (L.kind == L_EXCHANGE) return hipErrorInvalidValue;  // run by schedule_dispatch / the group driver
+  return Launch::visit(L, [&](const auto& args) { return launch_pick(pick_one(P, L), args, st); });
 }
 
 float* buf_of(msw_plan* P, int id) {
@@ -1278,26 +1281,17 @@ int rccl_exchange(msw_plan* P, const ExchangeArgs& a, hipStream_t st) {
   return MSW_OK;
 }
 
-template <int NT>
-int run_schedule(msw_plan* P, const std::vector<Launch>& q, hipStream_t st) {
+int schedule_dispatch(msw_plan* P, const std::vector<Launch>& q, hipStream_t st) {
   for (const Launch& L : q) {
     if (L.kind == L_EXCHANGE) {
       int rc = rccl_exchange(P, L.xch, st);
       if (rc) return rc;
     } else {
-      HIP_TRY(launch_one<NT>(L, st));
+      HIP_TRY(launch_one(P, L, st));
     }
   }
   P->kernels_per_step = (int)q.size();
   return MSW_OK;
-}
-
-int schedule_dispatch(msw_plan* P, const std::vector<Launch>& q, hipStream_t st) {
-  switch (P->NT) {
-    case 1: return run_schedule<1>(P, q, st);
-    case 2: return run_schedule<2>(P, q, st);
-    default: return run_schedule<4>(P, q, st);
-  }
 }
 
 // After a rollout's last step: the decoder of that step (the encoder launch of the rollout
@@ -1308,11 +1302,7 @@ int final_decode(msw_plan* P, hipStream_t st) {
   Launch L = P->sched_roll[0];
   L.enc.decode_only = 1;
   if (P->kn.trace_encode) L.enc.c.trace = nullptr;  // keep the last step's encoder marks
-  switch (P->NT) {
-    case 1: HIP_TRY(launch_one<1>(L, st)); break;
-    case 2: HIP_TRY(launch_one<2>(L, st)); break;
-    default: HIP_TRY(launch_one<4>(L, st)); break;
-  }
+  HIP_TRY(launch_one(P, L, st));
   return MSW_OK;
 }
 
@@ -1324,12 +1314,15 @@ void patch_forward(std::vector<Launch>& q, const float* x, float* y) {
       L.dec.dec.X = x;
       L.dec.dec.y = y;
     }
-    Epilogue* e = L.kind == L_EDGE_HOP ? &L.eh.epi : L.kind == L_HOP ? &L.hop.epi
-                 : L.kind == L_EPI ? &L.ep.epi : nullptr;
-    if (e && e->dec.on) {
-      e->dec.X = x;
-      e->dec.y = y;
-    }
+    if (L.kind == L_EDGE_MLP) continue;  // carries its layer's epilogue and does not run it
+    Launch::visit(L, [&](auto& a) {
+      using A = std::decay_t<decltype(a)>;
+      if constexpr (std::is_same_v<A, EdgeHopArgs> || std::is_same_v<A, HopArgs> || std::is_same_v<A, EpiArgs>)
+        if (a.epi.dec.on) {
+          a.epi.dec.X = x;
+          a.epi.dec.y = y;
+        }
+    });
   }
 }
 
@@ -1601,11 +1594,7 @@ int plan_create_impl(const msw_graph_desc* g, const msw_model_desc* m, int devic
         return rc;
 
   // ---- launch schedules (forward / rollout), per-launch weight regions, weight upload
-  switch (P->NT) {
-    case 1: HIP_TRY(prepare_kernels<1>()); break;
-    case 2: HIP_TRY(prepare_kernels<2>()); break;
-    default: HIP_TRY(prepare_kernels<4>()); break;
-  }
+  HIP_TRY(with_nt(P->NT, [](auto nt) { return prepare_kernels<nt>(); }));
   const size_t blob0 = P->blob.h.size();
   for (;;) {
     sched_step(P.get(), P->sched_fwd, false);
@@ -1784,7 +1773,6 @@ int loopback_exchange(msw_plan* const* plans, int k, const ExchangeArgs& a, hipS
   return MSW_OK;
 }
 
-template <int NT>
 int group_step(msw_plan* const* plans, int n, hipStream_t st) {
   const size_t L = plans[0]->sched_roll.size();
   for (size_t i = 0; i < L; ++i)
@@ -1794,7 +1782,7 @@ int group_step(msw_plan* const* plans, int n, hipStream_t st) {
         int rc = loopback_exchange(plans, k, l.xch, st);
         if (rc) return rc;
       } else {
-        HIP_TRY(launch_one<NT>(l, st));
+        HIP_TRY(launch_one(plans[k], l, st));
       }
     }
   return MSW_OK;
@@ -1875,11 +1863,7 @@ int msw_group_rollout(msw_plan* const* plans, int32_t num_plans, const float* co
     int rc = rollout_prologue(plans[k], x0[k], bc[k], bc_tstride[k], node_bc[k], n_bc[k], type_bc, T, out[k], st);
     if (rc) return rc;
   }
-  auto step = [&](hipStream_t s) {
-    return P0->NT == 1 ? group_step<1>(plans, num_plans, s)
-         : P0->NT == 2 ? group_step<2>(plans, num_plans, s)
-                       : group_step<4>(plans, num_plans, s);
-  };
+  auto step = [&](hipStream_t s) { return group_step(plans, num_plans, s); };
   msw_plan* G0 = plans[0];
   if (G0->group_graph) {
     // every part's launches and the halo copies of `steps` consecutive steps in one graph,
@@ -2061,17 +2045,8 @@ int msw_plan_schedule(const msw_plan* P, int32_t rollout, char* buf, int64_t cap
   static const char* const kind_name[] = {"encode", "edge_hop", "hop", "pool", "exchange", "epi", "edge_mlp", "decode"};
   std::string out;
   for (const Launch& L : rollout ? P->sched_roll : P->sched_fwd) {
-    Launch M = L;  // Launch::common() is not const
-    Pick p{};
-    if (L.kind == L_EXCHANGE) {
-      snprintf(p.name, sizeof(p.name), "exchange");
-    } else {
-      switch (P->NT) {
-        case 1: p = pick_one<1>(L); break;
-        case 2: p = pick_one<2>(L); break;
-        default: p = pick_one<4>(L); break;
-      }
-    }
+    Pick p = pick_one(P, L);
+    if (L.kind == L_EXCHANGE) snprintf(p.name, sizeof(p.name), "exchange");
     // iterations of the wave that makes the most: rounds of grid x per_wg units
     const long round = (long)p.grid * p.per_wg;
     const long iters = round > 0 ? (p.units + round - 1) / round : 0;
@@ -2080,7 +2055,7 @@ int msw_plan_schedule(const msw_plan* P, int32_t rollout, char* buf, int64_t cap
     snprintf(line, sizeof(line),
              "kind=%s\tvariant=%s\tnt=%d\tscale=%d\tprelu=%d\tgrid=%d\twaves=%d\tunits=%ld\tper_wg=%d\titers=%ld\t"
              "ragged=%d\tlds=%zu\n",
-             kind_name[L.kind], p.name, P->NT, L.scale, M.common().prelu, p.grid, p.waves, p.units, p.per_wg, iters,
+             kind_name[L.kind], p.name, P->NT, L.scale, L.common().prelu, p.grid, p.waves, p.units, p.per_wg, iters,
              ragged, p.lds);
     out += line;
   }
