@@ -382,6 +382,79 @@ int msw_zone_series_update(const msw_zones* zones, const float* pred, int32_t T,
 int msw_zone_series_launch(const msw_zones* zones, int32_t t_count, int32_t* grid,
                            int32_t* units_per_wg, int32_t* iters);
 
+/* On-device ensemble products: statistics ACROSS the members of an ensemble -- one mesh run with
+ * M boundary hydrographs, breach locations or initial states -- the third sibling: the flood maps
+ * reduce over time, the zone series over space, these over members.  The reference has no
+ * counterpart.
+ *
+ * An ensemble is M members, 1 <= M <= MSW_MAX_ENSEMBLE_MEMBERS, of n cells each.  Member m occupies
+ * rows member_row0[m] .. member_row0[m] + n - 1 of pred (device [N][2][T], graph numbering, as
+ * msw_rollout writes it): cell i of member m is row member_row0[m] + i.  For a batch of M copies of
+ * one mesh these are the finest-scale ranges of the batch (equal lengths, coarse rows in between).
+ * member_row0 is a HOST int64 [M] array in any order; the kernel takes it by value in its
+ * arguments.  A range may repeat and that member then counts twice.  Member order is the order of
+ * that list: every tie-break and every sum below uses it.  Larger ensembles, and merging the
+ * statistics of separately reduced groups, are out of scope. */
+#define MSW_MAX_ENSEMBLE_MEMBERS 64
+#define MSW_MAX_ENSEMBLE_RANKS 8
+
+typedef struct {            /* device pointers, NULL = not produced; leading stride T_out           */
+  int32_t* wet_members;     /* [n_thr][n][T_out] number of members with h_m > thr_k (strict)        */
+  float*   h_mean;          /* [n][T_out] (float)(S / (double)M), S = fp64 sum of (double)h_m added
+                               in member order from 0                                               */
+  float*   h_min;           /* [n][T_out] smallest h_m over the members                             */
+  float*   h_max;           /* [n][T_out] largest h_m over the members                              */
+} msw_ensemble_steps_out;
+
+/* Per-step statistics across members, the streaming pass: steps t_begin .. t_begin + t_count - 1
+ * of cells 0 .. n - 1, with h_m = pred[member_row0[m] + i][0][t], -> columns t_out0 ..
+ * t_out0 + t_count - 1 of the outputs; columns outside the window are not touched, the window's
+ * are overwritten (no initialisation needed).  thresholds: host float [n_thr],
+ * n_thr <= MSW_MAX_MAP_THRESHOLDS.
+ * Every depth of the window is read once, the discharge half of a row never.  No atomics, no
+ * scratch, no allocation: the results are the same bit for bit from call to call and however the
+ * horizon is cut into windows.  Inputs are finite; NaN behaviour is unspecified.
+ * Stream-ordered, no host synchronisation; needs no plan.  t_count = 0 or n = 0: no-op.
+ * MSW_ERR_INVALID (before any HIP call): NULL pred, out or member_row0, NULL thresholds with
+ * n_thr > 0, n_thr outside 0..4, M outside 1..64, a window outside [0, T], t_out0 < 0 or
+ * t_out0 + t_count > T_out, negative n or a negative member_row0. */
+int msw_ensemble_steps_update(const float* pred, int32_t T, int32_t t_begin, int32_t t_count,
+                              const int64_t* member_row0, int32_t M, int64_t n,
+                              const float* thresholds, int32_t n_thr, int32_t T_out, int32_t t_out0,
+                              const msw_ensemble_steps_out* out, void* stream);
+/* The launch msw_ensemble_steps_update makes for that size (from the code the launcher itself
+ * uses): workgroups, cells a workgroup takes per round, and the rounds of its cell loop, so that
+ * grid * cells_per_wg * iters >= n.  n = 0 or t_count = 0: grid and iters are 0.
+ * MSW_ERR_INVALID: negative n or t_count, M outside 1..64, a NULL output.  Host only. */
+int msw_ensemble_steps_launch(int64_t n, int32_t M, int32_t t_count, int32_t* grid,
+                              int32_t* cells_per_wg, int32_t* iters);
+
+typedef struct {                /* device pointers, NULL = not produced                             */
+  int32_t* exceed_members;      /* [n_thr][n]   number of members with value_m > thr_k (strict)     */
+  float*   mean;                /* [n]          as h_mean above, over values                        */
+  float*   rank_values;         /* [n_ranks][n] the value whose rank is ranks[j]                    */
+  int32_t* members_with_step;   /* [n]          number of members with steps_m >= 0                 */
+  int32_t* rank_steps;          /* [n_ranks][n] the step whose rank is ranks[j], or -1              */
+} msw_ensemble_maps_out;
+
+/* Order statistics across members of per-member maps, one shot, no carry-over.  values: device
+ * float [M][n] (e.g. each member's h_max) or NULL; steps: device int32 [M][n] (e.g. first_wet at
+ * one threshold, -1 = never) or NULL; the outputs of a NULL input are not produced.  ranks: host
+ * int32 [n_ranks], n_ranks <= MSW_MAX_ENSEMBLE_RANKS, each in 0..M-1, duplicates allowed.
+ *   values  member m has rank #{m' : v_m' < v_m, or v_m' == v_m and m' < m}: a stable ascending
+ *           sort by member order; rank 0 is the minimum, rank M - 1 the maximum.
+ *   steps   the same order with -1 sorting after every step: rank_steps[j] is -1 when fewer than
+ *           ranks[j] + 1 members have a step, else the first step by which at least ranks[j] + 1
+ *           members have been wet.
+ * No arithmetic touches the selected values: they are exact.  Inputs are finite; NaN behaviour is
+ * unspecified.  Stream-ordered, no host synchronisation, no allocation.  n = 0: no-op.
+ * MSW_ERR_INVALID (before any HIP call): NULL out, NULL thresholds with n_thr > 0, NULL ranks with
+ * n_ranks > 0, n_thr outside 0..4, M outside 1..64, n_ranks outside 0..8, a rank outside 0..M-1,
+ * negative n. */
+int msw_ensemble_maps(const float* values, const int32_t* steps, int32_t M, int64_t n,
+                      const float* thresholds, int32_t n_thr, const int32_t* ranks, int32_t n_ranks,
+                      const msw_ensemble_maps_out* out, void* stream);
+
 /* ---- Training: autograd through one SWEGNN processor ------------------------
  * Replaces the autograd of SWEGNN.forward (models/gnn.py:387-445) the reference trains through
  * in training_step (training/train.py:125-145).  Stateless: every buffer is device memory the

@@ -1428,6 +1428,8 @@ int64_t msw_struct_size(const char* name) {
   if (!strcmp(name, "msw_flood_maps")) return sizeof(msw_flood_maps);
   if (!strcmp(name, "msw_zone_series")) return sizeof(msw_zone_series);
   if (!strcmp(name, "msw_train_loss_desc")) return sizeof(msw_train_loss_desc);
+  if (!strcmp(name, "msw_ensemble_steps_out")) return sizeof(msw_ensemble_steps_out);
+  if (!strcmp(name, "msw_ensemble_maps_out")) return sizeof(msw_ensemble_maps_out);
   return -1;
 }
 

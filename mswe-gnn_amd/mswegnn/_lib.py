@@ -125,6 +125,20 @@ class MswZoneSeries(C.Structure):
                 ("h_max", C.c_void_p), ("q_max", C.c_void_p)]
 
 
+MAX_ENSEMBLE_MEMBERS = 64
+MAX_ENSEMBLE_RANKS = 8
+
+
+class MswEnsembleStepsOut(C.Structure):
+    _fields_ = [("wet_members", C.c_void_p), ("h_mean", C.c_void_p), ("h_min", C.c_void_p),
+                ("h_max", C.c_void_p)]
+
+
+class MswEnsembleMapsOut(C.Structure):
+    _fields_ = [("exceed_members", C.c_void_p), ("mean", C.c_void_p), ("rank_values", C.c_void_p),
+                ("members_with_step", C.c_void_p), ("rank_steps", C.c_void_p)]
+
+
 MAX_LOSS_RANGES = 64
 TRAIN_LOSS_RECORD = 12
 LOSS_TYPE = {"RMSE": 0, "MAE": 1}
@@ -174,6 +188,12 @@ SYMBOLS = [
                                          c_float_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(MswZoneSeries),
                                          C.c_void_p]),
     ("msw_zone_series_launch", C.c_int, [C.c_void_p, C.c_int32, c_int32_p, c_int32_p, c_int32_p]),
+    ("msw_ensemble_steps_update", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, c_int64_p, C.c_int32,
+                                            C.c_int64, c_float_p, C.c_int32, C.c_int32, C.c_int32,
+                                            C.POINTER(MswEnsembleStepsOut), C.c_void_p]),
+    ("msw_ensemble_steps_launch", C.c_int, [C.c_int64, C.c_int32, C.c_int32, c_int32_p, c_int32_p, c_int32_p]),
+    ("msw_ensemble_maps", C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, c_float_p, C.c_int32,
+                                    c_int32_p, C.c_int32, C.POINTER(MswEnsembleMapsOut), C.c_void_p]),
     ("msw_plan_create_part", C.c_int, [C.POINTER(MswGraphDesc), C.POINTER(MswModelDesc), C.c_int,
                                        C.POINTER(MswExchangeDesc), C.c_int32, C.POINTER(C.c_void_p)]),
     ("msw_comm_unique_id", C.c_int, [C.c_char_p]),
@@ -210,7 +230,8 @@ STRUCTS = {"msw_linear": MswLinear, "msw_mlp": MswMlp, "msw_swegnn": MswSwegnn,
            "msw_swegnn_train_desc": MswSwegnnTrainDesc, "msw_swegnn_grads": MswSwegnnGrads,
            "msw_mlp_train_desc": MswMlpTrainDesc, "msw_mlp_grads": MswMlpGrads,
            "msw_flood_maps": MswFloodMaps, "msw_zone_series": MswZoneSeries,
-           "msw_train_loss_desc": MswTrainLossDesc}
+           "msw_train_loss_desc": MswTrainLossDesc,
+           "msw_ensemble_steps_out": MswEnsembleStepsOut, "msw_ensemble_maps_out": MswEnsembleMapsOut}
 
 _lib = None
 
