@@ -455,6 +455,55 @@ int msw_ensemble_maps(const float* values, const int32_t* steps, int32_t M, int6
                       const float* thresholds, int32_t n_thr, const int32_t* ranks, int32_t n_ranks,
                       const msw_ensemble_maps_out* out, void* stream);
 
+/* Ensemble scores: the members of an ensemble verified against a truth run, the probabilistic
+ * sibling of msw_rollout_metrics.  Per cell i and step t, in fp64 on the converted float32 depths
+ * h_m = pred[member_row0[m] + i][0][t] and y = truth[truth_row0 + i][0][t_truth0 + (t - t_begin)]:
+ *   a = sum_m |h_m - y|     b = sum_{m<m'} |h_m - h_m'|     S = sum_m h_m (member order from 0)
+ *   e = S - M y             v = M sum_m h_m^2 - S^2         (M^2 times the population variance)
+ *   c_k = number of members with h_m > thr_k (strict, float32 against float32), o_k = y > thr_k.
+ * b is taken as sum_m (2 rank_m - M + 1) h_m over the stable ascending order of the members (the
+ * ranks of msw_ensemble_maps).  The kernel never divides by M or n: CRPS = sum a / (M n) -
+ * sum b / (M^2 n), the ensemble mean's MAE = sum |e| / (M n) and RMSE = sqrt(sum e^2 / (M^2 n)),
+ * the spread = sqrt(sum v / (M^2 n)); the Brier score and its decomposition follow from the table. */
+typedef struct {            /* device pointers, NULL = not produced                                  */
+  double*  sums;            /* [T_out][5] column t_out0 + (t - t_begin): the sums over the n cells of
+                               a, b, |e|, e^2, v; overwritten                                         */
+  int64_t* reliability;     /* [T_out][n_thr][M + 1][2]: per threshold and forecast count c = 0..M the
+                               number of cells with c_k = c, and how many of those have o_k;
+                               overwritten                                                            */
+  double*  cell_crps;       /* [n] ACCUMULATED: per step cell_crps[i] += M a - b, one addition per step
+                               in step order onto the carried value; the caller zeroes it.  Divided by
+                               M^2 and the steps seen: the time-mean CRPS map                         */
+} msw_ensemble_scores_out;
+
+/* Steps t_begin .. t_begin + t_count - 1 of cells 0 .. n - 1 -> columns t_out0 .. of sums and
+ * reliability (columns outside the window are not touched) and onto cell_crps.  truth: device
+ * [*][2][T_truth], the same layout as pred; it may be pred itself (a control run that is not a
+ * member).  member_row0, thresholds: host arrays, as for msw_ensemble_steps_update.
+ * Order: the cells are cut into blocks whose length depends on n alone; a block is added in cell
+ * order, the blocks in block order (a second small kernel over stream-ordered scratch), without
+ * atomics -- so sums is the same bit for bit however the horizon is cut into windows, and so is
+ * cell_crps.  Integers are exact.  A NaN member or truth depth makes the five terms of its cell
+ * and step NaN (the step's sums, the cell's cell_crps from then on) and counts as "not above".
+ * Every depth of the window is read once; rows outside the member ranges and the truth range and
+ * the discharge half of every row are never read.  Stream-ordered, no host synchronisation; needs
+ * no plan.  t_count = 0, n = 0 or no output asked for: no-op.
+ * MSW_ERR_INVALID (before any HIP call): NULL pred, truth, out or member_row0, NULL thresholds with
+ * n_thr > 0, n_thr outside 0..4, M outside 1..64, negative n, member_row0 or truth_row0, a window
+ * outside [0, T], truth columns outside [0, T_truth], output columns outside [0, T_out]. */
+int msw_ensemble_scores_update(const float* pred, int32_t T, int32_t t_begin, int32_t t_count,
+                               const int64_t* member_row0, int32_t M, int64_t n,
+                               const float* truth, int32_t T_truth, int32_t t_truth0, int64_t truth_row0,
+                               const float* thresholds, int32_t n_thr, int32_t T_out, int32_t t_out0,
+                               const msw_ensemble_scores_out* out, void* stream);
+/* The launch msw_ensemble_scores_update makes for that size (from the code the launcher itself
+ * uses): workgroups (= blocks of cells: a function of n alone), cells a workgroup takes per round
+ * and the rounds of its cell loop per tile of steps, so that grid * cells_per_wg * iters >= n.
+ * n = 0 or t_count = 0: grid and iters are 0.  MSW_ERR_INVALID: negative n or t_count, M outside
+ * 1..64, a NULL output.  Host only. */
+int msw_ensemble_scores_launch(int64_t n, int32_t M, int32_t t_count, int32_t* grid,
+                               int32_t* cells_per_wg, int32_t* iters);
+
 /* ---- Training: autograd through one SWEGNN processor ------------------------
  * Replaces the autograd of SWEGNN.forward (models/gnn.py:387-445) the reference trains through
  * in training_step (training/train.py:125-145).  Stateless: every buffer is device memory the

@@ -1430,6 +1430,7 @@ int64_t msw_struct_size(const char* name) {
   if (!strcmp(name, "msw_train_loss_desc")) return sizeof(msw_train_loss_desc);
   if (!strcmp(name, "msw_ensemble_steps_out")) return sizeof(msw_ensemble_steps_out);
   if (!strcmp(name, "msw_ensemble_maps_out")) return sizeof(msw_ensemble_maps_out);
+  if (!strcmp(name, "msw_ensemble_scores_out")) return sizeof(msw_ensemble_scores_out);
   return -1;
 }
 

@@ -139,6 +139,10 @@ class MswEnsembleMapsOut(C.Structure):
                 ("members_with_step", C.c_void_p), ("rank_steps", C.c_void_p)]
 
 
+class MswEnsembleScoresOut(C.Structure):
+    _fields_ = [("sums", C.c_void_p), ("reliability", C.c_void_p), ("cell_crps", C.c_void_p)]
+
+
 MAX_LOSS_RANGES = 64
 TRAIN_LOSS_RECORD = 12
 LOSS_TYPE = {"RMSE": 0, "MAE": 1}
@@ -194,6 +198,11 @@ SYMBOLS = [
     ("msw_ensemble_steps_launch", C.c_int, [C.c_int64, C.c_int32, C.c_int32, c_int32_p, c_int32_p, c_int32_p]),
     ("msw_ensemble_maps", C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, c_float_p, C.c_int32,
                                     c_int32_p, C.c_int32, C.POINTER(MswEnsembleMapsOut), C.c_void_p]),
+    ("msw_ensemble_scores_update", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, c_int64_p, C.c_int32,
+                                             C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, c_float_p,
+                                             C.c_int32, C.c_int32, C.c_int32, C.POINTER(MswEnsembleScoresOut),
+                                             C.c_void_p]),
+    ("msw_ensemble_scores_launch", C.c_int, [C.c_int64, C.c_int32, C.c_int32, c_int32_p, c_int32_p, c_int32_p]),
     ("msw_plan_create_part", C.c_int, [C.POINTER(MswGraphDesc), C.POINTER(MswModelDesc), C.c_int,
                                        C.POINTER(MswExchangeDesc), C.c_int32, C.POINTER(C.c_void_p)]),
     ("msw_comm_unique_id", C.c_int, [C.c_char_p]),
@@ -231,7 +240,8 @@ STRUCTS = {"msw_linear": MswLinear, "msw_mlp": MswMlp, "msw_swegnn": MswSwegnn,
            "msw_mlp_train_desc": MswMlpTrainDesc, "msw_mlp_grads": MswMlpGrads,
            "msw_flood_maps": MswFloodMaps, "msw_zone_series": MswZoneSeries,
            "msw_train_loss_desc": MswTrainLossDesc,
-           "msw_ensemble_steps_out": MswEnsembleStepsOut, "msw_ensemble_maps_out": MswEnsembleMapsOut}
+           "msw_ensemble_steps_out": MswEnsembleStepsOut, "msw_ensemble_maps_out": MswEnsembleMapsOut,
+           "msw_ensemble_scores_out": MswEnsembleScoresOut}
 
 _lib = None
 

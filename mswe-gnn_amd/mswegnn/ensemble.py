@@ -16,8 +16,16 @@ Member order is the order of the row ranges given; every sum and every tie-break
 Quantiles are numpy's ``inverted_cdf`` ones (:func:`quantile_rank`): a member's own value, never
 an interpolation.
 
-On CPU tensors the same interface runs :func:`_steps_torch` / :func:`_maps_torch`, plain torch
-restatements.
+Scores (C ABI ``msw_ensemble_scores_update``): :class:`EnsembleScores` verifies the ensemble
+against a truth run where both live -- the CRPS, the reliability table and the Brier score at the
+thresholds, the spread against the error of the ensemble mean -- from sums whose order of addition
+depends on the cell count alone, so that a rollout scored in chunks gives the bits of the whole.
+The scores are those of the M-member empirical distribution: E|X - y| - E|X - X'| / 2 with both
+expectations over the members (the "fair" CRPS would divide the second by M (M - 1) instead of
+M^2), and the spread is the population one (the unbiased variance is M / (M - 1) times its square).
+
+On CPU tensors the same interface runs :func:`_steps_torch` / :func:`_maps_torch` /
+:func:`_scores_torch`, plain torch restatements.
 """
 from __future__ import annotations
 
@@ -33,10 +41,12 @@ from .floodmaps import FloodMaps, _over_60, rollout_chunks
 from .metrics import finest_ranges
 from .rollout import adapt_batch_training
 
-__all__ = ["STEP_NAMES", "quantile_rank", "make_ensemble", "member_ranges", "EnsembleSteps", "ensemble_maps",
-           "EnsembleMaps", "rollout_ensemble"]
+__all__ = ["STEP_NAMES", "SCORE_NAMES", "quantile_rank", "make_ensemble", "member_ranges", "EnsembleSteps",
+           "ensemble_maps", "EnsembleMaps", "EnsembleScores", "ensemble_scores", "rollout_ensemble"]
 
 STEP_NAMES = ("wet_members", "h_mean", "h_min", "h_max")
+SCORE_NAMES = ("sums", "reliability", "cell_crps")
+SCORE_SUMS = ("a", "b", "abs_e", "e2", "v")
 _VALUE_MAPS = ("h_max", "q_max", "vel_max", "froude_max")
 _INT_MAX = torch.iinfo(torch.int32).max
 
@@ -367,25 +377,234 @@ class EnsembleMaps:
         return out
 
 
+# ---------------------------------------------------------------------------- scores
+_MIN_BLOCK, _BLOCKS, _MAX_BLOCK = 16, 2048, 32768
+
+
+def _block_cells(n):
+    """The cells of a summation block for n cells (csrc/scores.hip ``pick_launch``)."""
+    grown = -(-n // (_MIN_BLOCK * _BLOCKS)) * _MIN_BLOCK
+    return min(max(grown, _MIN_BLOCK), _MAX_BLOCK)
+
+
+def _sum_cells(x):
+    """[n, t] float64 -> [t]: the kernel's order -- blocks of ``_block_cells(n)`` consecutive
+    cells, a block added in cell order from 0, the blocks in block order.  It does not depend on t."""
+    n, t = x.shape
+    cpb = _block_cells(n)
+    nb = -(-n // cpb)
+    xb = torch.cat([x, torch.zeros(nb * cpb - n, t, dtype=x.dtype, device=x.device)]).view(nb, cpb, t)
+    part = torch.zeros(nb, t, dtype=x.dtype, device=x.device)
+    for j in range(cpb):
+        part = part + xb[:, j]
+    total = torch.zeros(t, dtype=x.dtype, device=x.device)
+    for b in range(nb):
+        total = total + part[b]
+    return total
+
+
+def _scores_torch(pred, row0, n, truth, thresholds=(0.05, 0.3)):
+    """The scores of ``pred`` [N, 2, t] across the members at rows ``row0`` against ``truth``
+    [n, t] (float32 depths) from plain torch ops -> ``sums`` [t, 5] float64, ``reliability``
+    [t, n_thr, M + 1, 2] int64 and ``crps_terms`` [n, t] float64 (M a - b per cell and step)."""
+    h = torch.stack([pred[r:r + n, 0, :].float() for r in row0])          # [M, n, t]
+    M, t = h.shape[0], h.shape[2]
+    y32 = truth.float()
+    hd, y = h.double(), y32.double()
+    a, S, Q = torch.zeros_like(y), torch.zeros_like(y), torch.zeros_like(y)
+    for m in range(M):                                                    # member order
+        a = a + (hd[m] - y).abs()
+        S = S + hd[m]
+        Q = Q + hd[m] * hd[m]
+    asc = torch.sort(h, dim=0).values.double()
+    b = torch.zeros_like(y)
+    for i in range(M):                                                    # b = sum_i (2 i - M + 1) h_(i), i from 0
+        b = b + float(2 * i - M + 1) * asc[i]
+    e = S - float(M) * y
+    v = float(M) * Q - S * S
+    bad = torch.isnan(a)                                                  # a NaN depth: every term is NaN
+    b, v = torch.where(bad, a, b), torch.where(bad, a, v)
+    sums = torch.stack([_sum_cells(x) for x in (a, b, e.abs(), e * e, v)], dim=1)
+    table = torch.zeros(t, len(thresholds), M + 1, 2, dtype=torch.int64, device=h.device)
+    col = torch.arange(t, device=h.device)[None, :] * (M + 1)
+    for k, thr in enumerate(thresholds):                                  # strict, float32 against float32
+        key = ((h > thr).sum(0) + col).reshape(-1)
+        obs = (y32 > thr).reshape(-1)
+        table[:, k, :, 0] = torch.bincount(key, minlength=t * (M + 1)).view(t, M + 1)
+        table[:, k, :, 1] = torch.bincount(key[obs], minlength=t * (M + 1)).view(t, M + 1)
+    return {"sums": sums, "reliability": table, "crps_terms": float(M) * a - b}
+
+
+def scores_launch(n, M, t_count):
+    """``(grid, cells_per_wg, iters)`` of ``msw_ensemble_scores_update`` for n cells, M members and
+    a window of ``t_count`` steps (host only); ``grid`` depends on n alone."""
+    g, c, it = C.c_int32(), C.c_int32(), C.c_int32()
+    L.check(L.lib().msw_ensemble_scores_launch(int(n), int(M), int(t_count), C.byref(g), C.byref(c), C.byref(it)))
+    return g.value, c.value, it.value
+
+
+class EnsembleScores:
+    """The ensemble at row ranges ``ranges`` (equal length n, member order = list order) scored
+    against a truth run over ``steps`` steps, column by column by successive :meth:`update` calls.
+    ``want``: what to produce (names of SCORE_NAMES, default all)."""
+
+    def __init__(self, ranges, steps, thresholds=(0.05, 0.3), want=None, device="cpu"):
+        self.row0, self.num_cells = _members(ranges)
+        self.num_members = len(self.row0)
+        self.steps = int(steps)
+        self.thresholds = tuple(float(t) for t in thresholds)
+        if len(self.thresholds) > L.MAX_MAP_THRESHOLDS:
+            raise ValueError(f"at most {L.MAX_MAP_THRESHOLDS} thresholds")
+        self.device = torch.device(device)
+        self.want = tuple(SCORE_NAMES if want is None else want)
+        unknown = set(self.want) - set(SCORE_NAMES)
+        if unknown:
+            raise ValueError(f"unknown scores {sorted(unknown)}; choose from {SCORE_NAMES}")
+        self.steps_seen = 0
+        n, M = self.num_cells, self.num_members
+        self.arrays = {}
+        if "sums" in self.want:          # every update overwrites its columns: no initialisation
+            self.arrays["sums"] = torch.empty(self.steps, len(SCORE_SUMS), dtype=torch.float64, device=self.device)
+        if "reliability" in self.want:
+            self.arrays["reliability"] = torch.empty(self.steps, len(self.thresholds), M + 1, 2, dtype=torch.int64,
+                                                     device=self.device)
+        if "cell_crps" in self.want:     # carried from call to call
+            self.arrays["cell_crps"] = torch.zeros(n, dtype=torch.float64, device=self.device)
+
+    def update(self, pred, truth, t_begin=0, t_count=None, truth_row0=0, truth_t0=None, stream=None):
+        """Score steps ``t_begin .. t_begin + t_count - 1`` of ``pred`` [N, 2, T] against columns
+        ``truth_t0 ..`` (default: the steps seen so far -- a truth that holds the whole horizon) of
+        rows ``truth_row0 .. truth_row0 + n - 1`` of ``truth`` [rows, 2, T_truth], into the next
+        ``t_count`` columns.  ``truth`` may be ``pred`` itself."""
+        if pred.dim() != 3 or pred.shape[1] != 2:
+            raise ValueError("pred must be [N, 2, T]")
+        if truth.dim() != 3 or truth.shape[1] != 2:
+            raise ValueError("truth must be [rows, 2, T_truth]")
+        T, Tt = int(pred.shape[2]), int(truth.shape[2])
+        t_begin, truth_row0 = int(t_begin), int(truth_row0)
+        t_count = T - t_begin if t_count is None else int(t_count)
+        truth_t0 = self.steps_seen if truth_t0 is None else int(truth_t0)
+        if t_begin < 0 or t_count < 0 or t_begin + t_count > T:
+            raise ValueError(f"steps [{t_begin}, {t_begin + t_count}) lie outside the rollout's {T}")
+        if truth_t0 < 0 or truth_t0 + t_count > Tt:
+            raise ValueError(f"truth columns [{truth_t0}, {truth_t0 + t_count}) lie outside the truth's {Tt}")
+        if pred.shape[0] < max(self.row0) + self.num_cells:
+            raise ValueError(f"pred has {pred.shape[0]} rows, the members reach row {max(self.row0) + self.num_cells}")
+        if truth_row0 < 0 or truth.shape[0] < truth_row0 + self.num_cells:
+            raise ValueError(f"truth has {truth.shape[0]} rows, the cells reach row {truth_row0 + self.num_cells}")
+        if pred.device != self.device or truth.device != self.device:
+            raise ValueError(f"pred is on {pred.device}, truth on {truth.device}, the scores on {self.device}")
+        if self.steps_seen + t_count > self.steps:
+            raise ValueError(f"{self.steps_seen} + {t_count} steps exceed the {self.steps} the arrays hold")
+        if t_count and self.num_cells and self.arrays:
+            if pred.is_cuda:
+                self._update_hip(pred, truth, T, Tt, t_begin, t_count, truth_row0, truth_t0, stream)
+            else:
+                n, at = self.num_cells, self.steps_seen
+                new = _scores_torch(pred[:, :, t_begin:t_begin + t_count], self.row0, n,
+                                    truth[truth_row0:truth_row0 + n, 0, truth_t0:truth_t0 + t_count], self.thresholds)
+                for k in ("sums", "reliability"):
+                    if k in self.arrays:
+                        self.arrays[k][at:at + t_count] = new[k]
+                if "cell_crps" in self.arrays:
+                    for t in range(t_count):     # one addition per step, in step order, onto the carried value
+                        self.arrays["cell_crps"] += new["crps_terms"][:, t]
+        self.steps_seen += t_count
+        return self
+
+    def _update_hip(self, pred, truth, T, Tt, t_begin, t_count, truth_row0, truth_t0, stream):
+        same = truth is pred
+        if pred.dtype != torch.float32 or not pred.is_contiguous():
+            pred = pred.float().contiguous()
+        if same:
+            truth = pred
+        elif truth.dtype != torch.float32 or not truth.is_contiguous():
+            truth = truth.float().contiguous()
+        out = L.MswEnsembleScoresOut(**{k: v.data_ptr() for k, v in self.arrays.items() if v.numel()})
+        row0 = (C.c_int64 * self.num_members)(*self.row0)
+        L.check(L.lib().msw_ensemble_scores_update(C.c_void_p(pred.data_ptr()), T, t_begin, t_count, row0,
+                                                   self.num_members, self.num_cells, C.c_void_p(truth.data_ptr()),
+                                                   Tt, truth_t0, truth_row0, _thr_array(self.thresholds),
+                                                   len(self.thresholds), self.steps, self.steps_seen, C.byref(out),
+                                                   _stream(stream, pred.device)))
+
+    def launch(self, t_count):
+        """``(grid, cells_per_wg, iters)`` of the update of a window of ``t_count`` steps."""
+        return scores_launch(self.num_cells, self.num_members, t_count)
+
+    def result(self):
+        """The scores of the steps seen so far as a dict (float64 throughout).  From ``sums``
+        [steps, 5] = the sums over the cells of a, b, |e|, e^2, v:
+          crps [steps] = sum a / (M n) - sum b / (M^2 n), ``crps_mean`` its mean over the steps
+          mae_mean     = sum |e| / (M n)            the ensemble mean's absolute error
+          rmse_mean    = sqrt(sum e^2 / (M^2 n))    ... and its RMSE
+          spread       = sqrt(sum v / (M^2 n))      the root of the mean population variance
+          spread_skill = spread / rmse_mean
+        from the table: ``reliability`` {thr: {forecast_prob [M + 1] = c / M, n [steps, M + 1] the
+        cells forecast c / M, observed [steps, M + 1] those of them above thr}} and ``brier``
+        {thr: [steps]} = the mean of (c / M - o)^2; ``cell_crps`` [n] = the time-mean CRPS map;
+        ``members``, ``steps``."""
+        t, M, n = self.steps_seen, self.num_members, self.num_cells
+        out = {"steps": t, "members": M}
+        if "sums" in self.arrays:
+            s = self.arrays["sums"][:t]
+            out["sums"] = s
+            out["crps"] = s[:, 0] / (M * n) - s[:, 1] / (M * M * n)
+            out["crps_mean"] = out["crps"].mean() if t else out["crps"].sum()
+            out["mae_mean"] = s[:, 2] / (M * n)
+            out["rmse_mean"] = torch.sqrt(s[:, 3] / (M * M * n))
+            out["spread"] = torch.sqrt(s[:, 4] / (M * M * n))
+            out["spread_skill"] = out["spread"] / out["rmse_mean"]
+        if "reliability" in self.arrays:
+            tab = self.arrays["reliability"][:t]
+            p = torch.arange(M + 1, dtype=torch.float64, device=self.device) / M
+            out["reliability"], out["brier"] = {}, {}
+            for k, thr in enumerate(self.thresholds):
+                cells, obs = tab[:, k, :, 0], tab[:, k, :, 1]
+                out["reliability"][thr] = {"forecast_prob": p, "n": cells, "observed": obs}
+                # (p - 1)^2 on the observed cells, p^2 on the others
+                out["brier"][thr] = (cells.double() * p * p - 2.0 * p * obs.double() + obs.double()).sum(1) / n
+        if "cell_crps" in self.arrays:
+            out["cell_crps"] = self.arrays["cell_crps"] / (M * M * max(t, 1))
+        return out
+
+
+def ensemble_scores(pred, truth, ranges, thresholds=(0.05, 0.3), want=None, t_begin=0, t_count=None, truth_row0=0,
+                    truth_t0=0, stream=None):
+    """:class:`EnsembleScores` in one shot: steps ``t_begin .. t_begin + t_count - 1`` (default:
+    to the end) of ``pred`` [N, 2, T] against ``truth`` -> ``EnsembleScores.result()``."""
+    t_count = int(pred.shape[2]) - int(t_begin) if t_count is None else int(t_count)
+    sc = EnsembleScores(ranges, max(t_count, 0), thresholds, want=want, device=pred.device)
+    return sc.update(pred, truth, t_begin, t_count, truth_row0, truth_t0, stream).result()
+
+
 def rollout_ensemble(model, batch, steps=None, chunk=16, thresholds=(0.05, 0.3), probs=(0.1, 0.5, 0.9),
-                     per_step=True, keep_rollout=False, of=("h_max", "first_wet"), temporal_res=None):
+                     per_step=True, keep_rollout=False, of=("h_max", "first_wet"), temporal_res=None, truth=None,
+                     truth_row0=0):
     """Roll out the ensemble ``batch`` (:func:`make_ensemble`) ``chunk`` steps at a time
     (``rollout_chunks``; ``chunk=None``: one ``model.rollout``) and feed every piece to an
     :class:`EnsembleMaps` and, with ``per_step``, an :class:`EnsembleSteps`: never more than one
     piece is held.  Returns ``{"maps": EnsembleMaps.result, "steps": EnsembleSteps.result or
-    None}``; ``keep_rollout=True`` returns ``(that, rollout)`` with the pieces concatenated (tests)."""
+    None}``; ``keep_rollout=True`` returns ``(that, rollout)`` with the pieces concatenated (tests).
+    With ``truth`` [rows, 2, >= steps] (the cells at rows ``truth_row0 ..``) every piece also feeds
+    an :class:`EnsembleScores`, whose result is added as ``"scores"``."""
     T = int(batch.y.shape[-1] if steps is None else steps)
     ranges = member_ranges(batch)
     dev = batch.x.device
     em = EnsembleMaps(ranges, thresholds, probs, of=of, device=dev)
     es = EnsembleSteps(ranges, T, thresholds, device=dev) if per_step else None
+    sc = EnsembleScores(ranges, T, thresholds, device=dev) if truth is not None else None
     kept = []
     pieces = [(0, model.rollout(batch, T))] if chunk is None else rollout_chunks(model, batch, T, chunk)
     for _, pred in pieces:
         em.update(pred)
         if es is not None:
             es.update(pred)
+        if sc is not None:
+            sc.update(pred, truth, truth_row0=truth_row0)
         if keep_rollout:
             kept.append(pred)
     out = {"maps": em.result(temporal_res), "steps": es.result() if es is not None else None}
+    if sc is not None:
+        out["scores"] = sc.result()
     return (out, torch.cat(kept, -1)) if keep_rollout else out
