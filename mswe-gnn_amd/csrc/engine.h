@@ -224,7 +224,42 @@ struct HopArgs {
   int nrows;         // destinations of the scale (local rows [0, nrows) = internal n0 + k)
   const int* rptr;   // [nrows + 1] CSR offsets (local destination order)
   const int2* redge; // [E] {internal source row, tile-padded s slot}, reference edge order
+  int stream;        // k_hop_rows: streaming stores (the encoder's size rule: nothing re-reads the
+                     // rows from cache), else plain stores
 };
+
+// Dense row-tile hop (k_hop_dense): a wave owns 16 consecutive destination rows, each lane row
+// holds its own in-edges (DenseRec), so messages and their in-order sum stay in registers.
+struct DenseHopArgs {
+  Common c;
+  int n0, nrows;           // internal rows [n0, n0 + nrows) of the scale
+  const DenseRec* recs;
+  const float* in;         // [Npad][F]
+  const float* s;          // [16 ntiles][F]
+  float* out;              // [Npad][F]
+  int filt_a;              // packed filter W_{k+1}, -1 = none
+  int grad, upwind;
+  const int* rptr;         // overflow walk (rows with more than kDenseInline in-edges)
+  const int2* redge;
+  int post_act; float post_slope;  // last hop of a layer whose epilogue is this and the store
+};
+// a layer's last hop whose epilogue has no MFMA work: the post-activation and the store only
+static inline bool bare_epilogue(const Epilogue& e) {
+  return e.np.a_u < 0 && e.np.a_v < 0 && e.np.a_o < 0 && e.uu_a < 0 && !e.dec.on;
+}
+// the arguments k_hop_dense takes for hop launch `a`, with the scale's inline in-edge records
+// and its CSR by destination (rows past the inline record)
+static inline DenseHopArgs dense_args(const HopArgs& a, const DenseRec* recs, const int* rptr, const int2* redge) {
+  DenseHopArgs d{};
+  d.c = a.c;
+  d.n0 = a.n0; d.nrows = a.nrows; d.recs = recs;
+  d.in = a.in; d.s = a.s; d.out = a.out;
+  d.filt_a = a.filt_a; d.grad = a.grad; d.upwind = a.upwind;
+  d.rptr = rptr; d.redge = redge;
+  d.post_act = a.last ? a.epi.post_act : 0;
+  d.post_slope = a.epi.post_slope;
+  return d;
+}
 
 // Mean pooling into the coarse rows + projection of the next processor.
 
@@ -340,6 +375,12 @@ struct Pick {
   int per_wg;       // units one workgroup takes per round
 };
 
+// The dense hop's workgroup is ONE wave (one row tile): the dispatcher then spreads a scale's
+// row tiles over every CU (zenodo4's finest scale: 649 waves on 256 CUs), where 4-wave
+// workgroups put them on 163 CUs, four gathering waves behind one CU's address path each
+// (measured -7 % of the step against one wave).  No barrier, no LDS: nothing
+// is shared inside a workgroup.
+
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
 // one tile per wave while that grid is resident at once; grid-stride loop beyond that
@@ -378,7 +419,7 @@ static inline hipError_t launch_pick(const Pick& p, const A& a, hipStream_t st) 
 // (kernels/k_pick.h) maps a key to the kernel, its workgroup and its dynamic-LDS rule; the
 // picks, the residency queries and prepare_kernels all go through it.
 enum Family { K_ENCODE, K_ENCODE_COOP, K_EDGE_HOP, K_EDGE_COOP, K_EDGE_MLP, K_HOP, K_HOP_ROWS, K_HOP_SPLIT,
-              K_HOP_COOP, K_POOL_ROWS, K_POOL_EDGE, K_EPI, K_DECODE, K_FAMILIES };
+              K_HOP_COOP, K_HOP_DENSE, K_POOL_ROWS, K_POOL_EDGE, K_EPI, K_DECODE, K_FAMILIES };
 struct VariantKey {
   int family;
   int prelu = 0;   // every MLP activation is PReLU (Common::prelu)
@@ -395,6 +436,7 @@ template <int NT> Pick pick_encode(const EncodeArgs& a);
 template <int NT> Pick pick_edge_hop(const EdgeHopArgs& a);
 template <int NT> Pick pick_edge_mlp(const EdgeHopArgs& a);
 template <int NT> Pick pick_hop(const HopArgs& a);
+template <int NT> Pick pick_hop_dense(const HopArgs& a);  // the same launch as a dense row-tile hop
 template <int NT> Pick pick_pool(const PoolArgs& a);
 template <int NT> Pick pick_epi(const EpiArgs& a);
 template <int NT> Pick pick_decode(const DecodeArgs& a);

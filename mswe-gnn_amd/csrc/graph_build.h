@@ -104,6 +104,49 @@ struct HostXchScale {
   std::vector<XchPeer> peers;
 };
 
+// Dense row-tile hop (k_hop_dense, latency-bound scales): the in-edges of one destination row,
+// one 32-B record (two 16-B loads): the first kDenseInline {internal source row, tile-padded s
+// slot} pairs in reference edge order, an absent pair holds x = -1.  A row with more in-edges
+// has the fourth pair's slot stored as ~slot (negative): the rest follow in the CSR.
+constexpr int kDenseInline = 4;
+struct alignas(16) DenseRec {
+  I2 e[kDenseInline];
+};
+struct HostDense {
+  std::vector<DenseRec> recs;  // [16 ceil(ns / 16)] by local destination row
+  std::vector<int> rptr;       // [ns + 1] CSR offsets by local destination (the overflow walk)
+  std::vector<I2> redge;       // {internal source row, tile-padded s slot} per CSR edge
+};
+// From the scale's lane records (make_recs): node lane j of an edge tile names destination n and
+// its slots [q0, q1) of that tile, in reference edge order.
+inline HostDense build_dense(const std::vector<LaneRec>& recs, int n0, int ns) {
+  HostDense d;
+  const int padded = (ns + kRowsPerWave - 1) / kRowsPerWave * kRowsPerWave;
+  d.recs.assign((size_t)std::max(padded, kRowsPerWave), DenseRec{{{-1, 0}, {-1, 0}, {-1, 0}, {-1, 0}}});
+  std::vector<int> first(ns, 0), deg(ns, 0);  // first tile-padded slot and in-degree per row
+  for (size_t t = 0; t * kRowsPerWave < recs.size(); ++t)
+    for (int j = 0; j < kRowsPerWave; ++j) {
+      const LaneRec& r = recs[t * kRowsPerWave + j];
+      if (r.n < 0) continue;
+      const int k = r.n - n0;
+      if (k < 0 || k >= ns) continue;
+      first[k] = (int)(t * kRowsPerWave) + (r.q & 255);
+      deg[k] = (r.q >> 8) - (r.q & 255);
+    }
+  d.rptr.assign(ns + 1, 0);
+  for (int k = 0; k < ns; ++k) d.rptr[k + 1] = d.rptr[k] + deg[k];
+  d.redge.assign(std::max(d.rptr[ns], 1), I2{n0, 0});
+  for (int k = 0; k < ns; ++k)
+    for (int q = 0; q < deg[k]; ++q) {
+      const I2 e{recs[first[k] + q].src, first[k] + q};
+      d.redge[d.rptr[k] + q] = e;
+      if (q < kDenseInline) d.recs[k].e[q] = e;
+    }
+  for (int k = 0; k < ns; ++k)
+    if (deg[k] > kDenseInline) d.recs[k].e[kDenseInline - 1].y = ~d.recs[k].e[kDenseInline - 1].y;
+  return d;
+}
+
 // Stable counting sort by key in [0, nkeys): rowptr + order (original indices).
 inline void csr_build(int nkeys, const std::vector<int>& key, std::vector<int>& rowptr, std::vector<int>& order) {
   rowptr.assign(nkeys + 1, 0);

@@ -169,7 +169,7 @@ __global__ __launch_bounds__(64 * kRowHopWaves) void k_hop_rows(HopArgs a) {
   [[maybe_unused]] const int lane = threadIdx.x & 63;
   const int w = wave_id();
   const int stride = gridDim.x * kRowHopWaves;
-  MSW_PIN(stride, a.nrows, a.rptr, a.redge, a.n0, a.in, a.s, a.out, a.c.W, a.filt_a, a.grad, a.upwind);
+  MSW_PIN(stride, a.nrows, a.rptr, a.redge, a.n0, a.in, a.s, a.out, a.c.W, a.filt_a, a.grad, a.upwind, a.stream);
   const int ntile = (a.nrows + kRowsPerWave - 1) / kRowsPerWave;
   f32x4 wf[NT][NT];  // the filter in registers (in LDS: equal, profiles/r03/ab_rows_variants.jsonl)
   load_filter<NT>(wf, a.c.W, a.filt_a, lane);
@@ -233,8 +233,130 @@ __global__ __launch_bounds__(64 * kRowHopWaves) void k_hop_rows(HopArgs a) {
 #pragma unroll
     for (int t = 0; t < NT; ++t) res[t] = od[t];
     apply_filter_regs<NT>(res, agg, a.filt_a, wf);
-    if (valid) store_row<NT, true>(a.out + n * F, res, NT, g);  // streaming (large meshes only)
+    // streaming where the mesh is past the caches (HopArgs::stream), else the next hop re-reads
+    if (valid) {
+      if (a.stream)
+        store_row<NT, true>(a.out + n * F, res, NT, g);
+      else
+        store_row<NT>(a.out + n * F, res, NT, g);
+    }
   }
+}
+
+// ---------------------------------------------------------------------------- dense row-tile hop
+// Latency-bound scales (the row tiles resident in one round): the row layout of k_hop_rows built
+// for the dependent-launch regime.  One wave = one workgroup (the dispatcher spreads the row tiles
+// over every CU) owns 16 CONSECUTIVE destination rows, one tile, no loop; lane row j reads its
+// 32-B in-edge record (DenseRec: up to four {source row, s slot} pairs inline) and issues its own
+// row and its first three edges' source and s rows together (14 row loads per lane at F = 32);
+// the fourth inline pair is fetched only by a wave that holds a row with four in-edges; the
+// activity predicate, the messages and agg = ((0 + m_0) + m_1) + ... in reference edge order
+// stay in registers (no LDS, no barrier), all 16 rows of the filter MFMA are live, the store is
+// plain (the next hop re-reads the rows from cache).  Rows with more in-edges walk the rest
+// from the scale's CSR by destination, one edge per trip (rare: in-degree <= 3 on the meshes
+// here).  The arithmetic is k_hop's operation for operation, as k_hop_rows': bit-identical.
+// LAST: a layer's last hop whose epilogue is the post-activation and the store (node_epilogue
+// without projections, unpool U or decoder).
+template <int NT, int ACT, bool LAST>
+__global__ __launch_bounds__(64) void k_hop_dense(DenseHopArgs a) {
+#pragma clang fp contract(off)
+  static_assert(NT <= 2, "4 x 2 NT + NT row loads per lane: F <= 32");
+  constexpr int F = 16 * NT, DC = kDenseInline;
+  const int lane = threadIdx.x & 63, g = lane >> 4, j = lane & 15;
+  MSW_PIN(a.c.xcd, a.nrows, a.recs, a.n0, a.in, a.s, a.out, a.c.W, a.filt_a, a.grad, a.upwind);
+  const int xb = logical_block(a.c);
+  if (xb < 0) return;
+  if (xb * kRowsPerWave >= a.nrows) return;  // a workgroup past the scale's last row tile (packed grids)
+  const int k = xb * kRowsPerWave + j;
+  MSW_MARK(a.c, 0);
+  f32x4 wf[NT][NT];
+  load_filter<NT>(wf, a.c.W, a.filt_a, lane);
+  // (the records and the scale's rows are padded to whole tiles: a lane past nrows reads an
+  // empty record and its own padding row, and stores nothing)
+  const bool valid = k < a.nrows;
+  const int4 r0 = reinterpret_cast<const int4*>(a.recs)[2 * (size_t)k];
+  const int4 r1 = reinterpret_cast<const int4*>(a.recs)[2 * (size_t)k + 1];
+  const size_t n = (size_t)a.n0 + k;
+  f32x4 od[NT];
+  load_row<NT>(od, a.in + n * F, g);
+  MSW_MARK(a.c, 1);
+  const bool more = r1.z >= 0 && r1.w < 0;  // the fourth slot stored as ~slot: the CSR holds more
+  const int src[DC] = {r0.x, r0.z, r1.x, r1.z};
+  const int slot[DC] = {r0.y, r0.w, r1.y, r1.w < 0 ? ~r1.w : r1.w};
+  f32x4 os[DC][NT], sv[DC][NT];
+  // absent edges read the row's own entries (never used): its own row and its first edge's s
+  // row, not one fixed row -- every wave of the launch would ask one L2 channel for that line at once
+  const size_t own_s = src[0] >= 0 ? (size_t)slot[0] : 0;
+  auto fetch = [&](int u) {
+    const bool has = src[u] >= 0;
+    load_row<NT>(os[u], a.in + (has ? (size_t)src[u] : n) * F, g);
+    load_row<NT>(sv[u], a.s + (has ? (size_t)slot[u] : own_s) * F, g);
+  };
+#pragma unroll
+  for (int u = 0; u < DC - 1; ++u) fetch(u);
+  const bool four = __any(src[DC - 1] >= 0);  // wave-uniform (no such row on the triangular meshes here)
+#pragma unroll
+  for (int t = 0; t < NT; ++t) os[DC - 1][t] = sv[DC - 1][t] = zero4();
+  if (four) fetch(DC - 1);
+  MSW_MARK(a.c, 4);
+  float rd = 0.f;
+#pragma unroll
+  for (int t = 0; t < NT; ++t) rd += hsum(od[t]);
+  const bool zd = row_sum(rd) != 0.f;
+  f32x4 agg[NT];
+#pragma unroll
+  for (int t = 0; t < NT; ++t) agg[t] = zero4();
+  auto edge = [&](const f32x4(&so)[NT], const f32x4(&se)[NT], bool has) {
+    float rs = 0.f;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) rs += hsum(so[t]);
+    const bool act = (row_sum(rs) != 0.f) || zd;  // gnn.py:408-411
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      f32x4 gv;
+      if (a.grad) {
+        gv = od[t] - so[t];
+        if (a.upwind) {
+          gv.x = gv.x < 0.f ? 0.f : gv.x; gv.y = gv.y < 0.f ? 0.f : gv.y;
+          gv.z = gv.z < 0.f ? 0.f : gv.z; gv.w = gv.w < 0.f ? 0.f : gv.w;
+        }
+      } else {
+        gv = so[t];
+      }
+      const f32x4 m = act ? gv * se[t] : zero4();
+      const f32x4 sum = agg[t] + m;
+      agg[t] = has ? sum : agg[t];
+    }
+  };
+#pragma unroll
+  for (int u = 0; u < DC - 1; ++u) edge(os[u], sv[u], src[u] >= 0);
+  if (four) edge(os[DC - 1], sv[DC - 1], src[DC - 1] >= 0);
+  if (__any(more)) {  // wave-uniform
+    const int q0 = a.rptr[valid ? k : 0];
+    const int deg = more ? a.rptr[k + 1] - q0 : 0;
+    for (int q = DC; __any(q < deg); ++q) {
+      const bool has = q < deg;
+      const int2 e = has ? a.redge[q0 + q] : int2{(int)n, 0};
+      f32x4 so[NT], se[NT];
+      load_row<NT>(so, a.in + (size_t)e.x * F, g);
+      load_row<NT>(se, a.s + (size_t)e.y * F, g);
+      edge(so, se, has);
+    }
+  }
+  MSW_MARK(a.c, 7);
+  f32x4 res[NT];
+#pragma unroll
+  for (int t = 0; t < NT; ++t) res[t] = od[t];
+  apply_filter_regs<NT>(res, agg, a.filt_a, wf);
+  MSW_MARK(a.c, 8);
+  if constexpr (LAST) {
+    if (a.post_act) {
+      act_tiles<-1, NT>(res, a.post_act, a.post_slope);
+      mask_pad<ACT, NT>(res, a.c.fl, g);
+    }
+  }
+  if (valid) store_row<NT>(a.out + n * F, res, NT, g);
+  MSW_MARK(a.c, 9);
 }
 
 // ---------------------------------------------------------------------------- feature-split middle hop

@@ -50,6 +50,7 @@ int resident_blocks(const VariantKey& k, int floats) {
   template Pick pick_edge_hop<NT>(const EdgeHopArgs&);                            \
   template Pick pick_edge_mlp<NT>(const EdgeHopArgs&);                            \
   template Pick pick_hop<NT>(const HopArgs&);                                     \
+  template Pick pick_hop_dense<NT>(const HopArgs&);                               \
   template Pick pick_pool<NT>(const PoolArgs&);                                   \
   template Pick pick_epi<NT>(const EpiArgs&);                                     \
   template Pick pick_decode<NT>(const DecodeArgs&);                               \

@@ -91,6 +91,13 @@ static Variant variant_of(const VariantKey& k) {
       if constexpr (NT >= 2) return {(const void*)k_hop_split<NT>, kWaves, LDS_NONE, 0};
       return none;
     case K_HOP_COOP: return {hop_coop_kernel<NT>(k.prelu), kWaves, LDS_STAGED, mx(kWaves)};
+    case K_HOP_DENSE:  // F <= 32; a middle hop has no activation
+      if constexpr (NT <= 2) {
+        const void* f = !k.last ? (const void*)k_hop_dense<NT, 1, false>
+                                : act((const void*)k_hop_dense<NT, 1, true>, (const void*)k_hop_dense<NT, -1, true>);
+        return {f, 1, LDS_NONE, 0};  // one wave (one row tile) per workgroup
+      }
+      return none;
     case K_POOL_ROWS:
       return by_flag(k.loop, [&](auto lp) {
         constexpr bool L = decltype(lp)::value;
@@ -224,6 +231,16 @@ Pick pick_hop(const HopArgs& a) {
   const Variant v = variant_of<NT>({K_HOP, a.c.prelu, last, loop});
   return pick_make<NT>(v, pick_name(nm, "hop", {{loop, "loop"}, {last, "last"}, {!last, "mid"}}), tile_grid(a), !loop,
                        last ? a.reg.len : 0, a.ntiles, v.waves);
+}
+
+// dense row-tile hop (latency-bound scales, Launch::dense): one row tile per one-wave workgroup, one round
+template <int NT>
+Pick pick_hop_dense(const HopArgs& a) {
+  if (a.nrows <= 0) return Pick{};
+  char nm[40];
+  const int nt = cdiv(a.nrows, kRowsPerWave);
+  return pick_make<NT>(variant_of<NT>({K_HOP_DENSE, a.c.prelu, a.last != 0}),
+                       pick_name(nm, "hop dense", {{a.last != 0, "last"}}), nt, 1, 0, nt, 1);
 }
 
 template <int NT>

@@ -182,8 +182,11 @@ struct ScaleCSR {
   int nchunks = 0;
   int* rptr = nullptr;          // row-layout middle hops (k_hop_rows, large scales): CSR by
   int2* redge = nullptr;        // destination, {source row, s slot} per edge
+  DenseRec* drecs = nullptr;    // dense row-tile hops (k_hop_dense, latency-bound scales): inline
+  int* dptr = nullptr;          // in-edge records per destination row, and the CSR by destination
+  int2* dedge = nullptr;        // for rows past the inline record (upload_dense)
 
-  std::vector<int> porig;       // tile-padded edge slot -> original edge id, -1 = padding
+  std::vector<int> porig;      // tile-padded edge slot -> original edge id, -1 = padding
   std::vector<LaneRec> hrecs;   // host copy of recs (fused pooling slots, PoolSlot)
 };
 
@@ -269,6 +272,8 @@ struct ExchangeArgs {
 struct Launch {
   int kind;
   int scale;                    // destination scale (bench hook)
+  int dense;                    // L_HOP: runs as the dense row-tile hop (k_hop_dense, DenseHopArgs
+                                // formed at launch from the hop's arguments and the scale's records)
   union {
     EncodeArgs enc;
     EdgeHopArgs eh;
@@ -316,6 +321,7 @@ struct Knobs {
   int enc_coop = -1;        // MSW_ENC_COOP        cooperative encoder: -1 size rule, 0 / 1 force
   int eh_loop = 0;          // MSW_EH_LOOP         grid-stride fused edge hops at any size
   int hop_split = -1;       // MSW_HOP_SPLIT       feature-split middle hops: -1 = F = 64 rule
+  int hop_dense = 1;        // MSW_HOP_DENSE       dense row-tile hops of latency-bound scales (F <= 32), 0 off
   int pool_wide = 1;        // MSW_POOL_WIDE       2F / 16 waves per pooling tile
   int tile_pack = 1;        // MSW_TILE_PACK       degree-aware destination order
   int xcd_max = 1;          // MSW_XCD_MAX         XCD packing of small grids (0 = all eight XCDs)
@@ -336,7 +342,7 @@ inline Knobs knobs_from_env() {
       {"MSW_UNPOOL_FUSE", &k.unpool_fuse}, {"MSW_DEFER_DECODE", &k.defer_decode}, {"MSW_HOP_ROWS", &k.hop_rows},
       {"MSW_COOP2_DIRECT", &k.coop2_direct}, {"MSW_COOP2_F64", &k.coop2_f64}, {"MSW_ENC_COOP", &k.enc_coop},
       {"MSW_EH_LOOP", &k.eh_loop},
-      {"MSW_HOP_SPLIT", &k.hop_split}, {"MSW_POOL_WIDE", &k.pool_wide}, {"MSW_TILE_PACK", &k.tile_pack},
+      {"MSW_HOP_SPLIT", &k.hop_split}, {"MSW_HOP_DENSE", &k.hop_dense}, {"MSW_POOL_WIDE", &k.pool_wide}, {"MSW_TILE_PACK", &k.tile_pack},
       {"MSW_XCD_MAX", &k.xcd_max}, {"MSW_COOP_WAVES", &k.coop_waves},
       {"MSW_EPI_SPLIT_TILES", &k.epi_split_tiles}, {"MSW_TRACE_ENCODE", &k.trace_encode},
       {"MSW_GRID_CAP", &k.grid_cap}};
@@ -1077,6 +1083,29 @@ constexpr int kHopLoopTiles = 65536;
 constexpr int kRowHopMinTiles = kHopLoopTiles;
 // MSW_HOP_ROWS=2: every middle hop in the row layout, at any size (parity tests)
 bool row_hops_forced(const msw_plan* P) { return P->kn.hop_rows == 2; }
+// Dense row-tile hops (k_hop_dense) on scales of at most this many row tiles (two waves per
+// SIMD in one round), and only while the chip holds them all at once: beyond, the launch is
+// no longer latency-bound and the edge tiles' fewer, wider gathers win
+// (profiles/densehop/ab_workloads.txt; MSW_HOP_DENSE=0 switches the kernel off)
+constexpr int kDenseMaxTiles = 2048;
+bool dense_hops(const msw_plan* P, const ScaleCSR& c) {
+  if (P->NT > 2 || P->part_rank >= 0 || P->kn.grid_cap > 0 || P->kn.hop_dense == 0) return false;
+  if (row_hops_forced(P) || (P->kn.hop_split > 0 && P->NT >= 2)) return false;  // those switches force their kernels
+  const int nt = cdiv(c.ns, kRowsPerWave);
+  if (nt <= 0 || c.ntiles <= 0 || nt > kDenseMaxTiles) return false;
+  return nt <= resident_of(P, {K_HOP_DENSE, P->prelu, 1}, 0);  // one-wave workgroups
+}
+// The inline in-edge records and the overflow CSR of the scales that run the dense hop.
+int upload_dense(msw_plan* P) {
+  for (ScaleCSR& c : P->sc) {
+    if (!dense_hops(P, c)) continue;
+    const HostDense d = build_dense(c.hrecs, c.n0, c.ns);
+    int rc;
+    if ((rc = pupload(P, &c.drecs, d.recs)) || (rc = pupload(P, &c.dptr, d.rptr)) || (rc = pupload(P, &c.dedge, d.redge)))
+      return rc;
+  }
+  return MSW_OK;
+}
 constexpr long kEncCoopWaves = 4096;
 // set_grid_cap, one function per launch kind: the residency figures of a launch and the
 // variant choices that go by them (cooperative / split / row-layout / streaming / direct)
@@ -1144,7 +1173,8 @@ void cap_edge_hop(const msw_plan* P, EdgeHopArgs& a) {
   }
   if ((a.pool.slots || a.pool.parent) && !a.coop) a.coop = 2;  // F = 64 fused: two waves per tile, any grid
 }
-void cap_hop(const msw_plan* P, HopArgs& h) {
+void cap_hop(const msw_plan* P, Launch& L) {
+  HopArgs& h = L.hop;
   caps(P, h, {K_HOP, h.c.prelu, h.last}, h.reg.len);
   // one tile per wave below kHopLoopTiles: the grid-stride variant measured 1.1-1.6 % slower on the batch of 8 and
   // dk15, equal on the 1M-node mesh whose finest hop alone it runs 3 % faster
@@ -1163,11 +1193,24 @@ void cap_hop(const msw_plan* P, HopArgs& h) {
     h.rows = 1;
     h.split = 0;
     h.max_blocks = resident_of(P, {K_HOP_ROWS}, 0);
+    // ... streaming its stores by the encoder's size rule: more 64-row chunks than the chip holds
+    // encoder workgroups (below, the next hop re-reads the rows from cache)
+    int enc_floats = 0;
+    for (const Launch& E : P->sched_fwd)
+      if (E.kind == L_ENCODE) enc_floats = E.enc.lds_floats;
+    const int enc_fit = resident_of(P, {K_ENCODE, P->prelu}, enc_floats);
+    h.stream = enc_fit > 0 && P->Npad / kRowsPerBlock > enc_fit;
   }
+  // dense row-tile hop where the scale has its records (dense_hops): middle hops, and a last
+  // hop whose epilogue is the post-activation and the store -- on every scale: with the pooling
+  // fused into the next scale's first launch, the down-processors' last hops of the coarser
+  // scales have such an epilogue too, and leave k_hop_coop
+  L.dense = P->sc[L.scale].drecs && !h.rows && !tile_loop(h) && (!h.last || bare_epilogue(h.epi));
+  if (L.dense) h.split = 0;
   // a last hop with an epilogue on few tiles: P = F / 16 waves per tile (k_hop_coop)
   const int pw = P->NT >= 2 ? P->NT : 0;
   h.coop = 0;
-  if (h.last && pw && !tile_loop(h) && P->coop_waves > 0 && (long)pw * h.ntiles <= P->coop_waves &&
+  if (h.last && !L.dense && pw && !tile_loop(h) && P->coop_waves > 0 && (long)pw * h.ntiles <= P->coop_waves &&
       (pw * h.ntiles + kWaves - 1) / kWaves <= resident_of(P, {K_HOP_COOP, h.c.prelu, 1, 0, pw}, h.reg.len))
     h.coop = pw;
 }
@@ -1199,7 +1242,7 @@ void set_grid_cap(const msw_plan* P, Launch& L) {
     case L_ENCODE: return cap_encode(P, L.enc);
     case L_EDGE_MLP: return cap_edge_mlp(P, L.eh);
     case L_EDGE_HOP: return cap_edge_hop(P, L.eh);
-    case L_HOP: return cap_hop(P, L.hop);
+    case L_HOP: return cap_hop(P, L);
     case L_EPI: return caps(P, L.ep, {K_EPI, L.ep.c.prelu, 1}, L.ep.reg.len);
     case L_POOL: return cap_pool(P, L.pool);
     default: return;  // exchanges and the forward decoder have no grid to cap
@@ -1226,7 +1269,7 @@ Pick pick_one(const Launch& L) {
     case L_ENCODE: return pick_encode<NT>(L.enc);
     case L_EDGE_HOP: return pick_edge_hop<NT>(L.eh);
     case L_EDGE_MLP: return pick_edge_mlp<NT>(L.eh);
-    case L_HOP: return pick_hop<NT>(L.hop);
+    case L_HOP: return L.dense ? pick_hop_dense<NT>(L.hop) : pick_hop<NT>(L.hop);
     case L_POOL: return pick_pool<NT>(L.pool);
     case L_EPI: return pick_epi<NT>(L.ep);
     case L_DECODE: return pick_decode<NT>(L.dec);
@@ -1238,6 +1281,10 @@ Pick pick_one(const msw_plan* P, const Launch& L) {
 }
 hipError_t launch_one(const msw_plan* P, const Launch& L, hipStream_t st) {
   if (L.kind == L_EXCHANGE) return hipErrorInvalidValue;  // run by schedule_dispatch / the group driver
+  if (L.kind == L_HOP && L.dense) {  // k_hop_dense takes its own arguments
+    const ScaleCSR& c = P->sc[L.scale];
+    return launch_pick(pick_one(P, L), dense_args(L.hop, c.drecs, c.dptr, c.dedge), st);
+  }
   return Launch::visit(L, [&](const auto& args) { return launch_pick(pick_one(P, L), args, st); });
 }
 
@@ -1598,6 +1645,7 @@ int plan_create_impl(const msw_graph_desc* g, const msw_model_desc* m, int devic
 
   // ---- launch schedules (forward / rollout), per-launch weight regions, weight upload
   HIP_TRY(with_nt(P->NT, [](auto nt) { return prepare_kernels<nt>(); }));
+  if ((rc = upload_dense(P.get()))) return rc;
   const size_t blob0 = P->blob.h.size();
   for (;;) {
     sched_step(P.get(), P->sched_fwd, false);
