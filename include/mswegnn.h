@@ -504,6 +504,96 @@ int msw_ensemble_scores_update(const float* pred, int32_t T, int32_t t_begin, in
 int msw_ensemble_scores_launch(int64_t n, int32_t M, int32_t t_count, int32_t* grid,
                                int32_t* cells_per_wg, int32_t* iters);
 
+/* Raster products: per-cell maps and rollout frames resampled onto a regular grid, the last step
+ * between a rollout on the device and a layer a GIS, a warning system or a web viewer takes.  The
+ * reference resamples on the host with a plotting library (plot_faces, a PolyCollection); there is
+ * no numerical counterpart.  Every output is an index decided by fp64 predicates evaluated in the
+ * written order below, or a 32-bit word copied unchanged: all of it is exact.
+ *
+ * Geometry of ONE mesh scale: node_xy float64 [num_nodes][2], face_nodes int32 [num_faces][3]
+ * (triangles; the signature admits nothing else), optional face_row int32 [num_faces]: the graph
+ * row that holds face f's value (NULL: f; -1: the face has no value -- it still takes part in
+ * the location and yields -1).  All three are HOST arrays.  The grid: pixel (i, j), element
+ * j * width + i, has the centre px = x0 + (double)i * dx, py = y0 + (double)j * dy (one multiply,
+ * one add, no fma); dx and dy may be negative (north-up rasters).
+ *
+ * Edge function of the directed edge (u -> v) at a pixel: p = whichever of u, v has the LOWER
+ * vertex index, q = the other;
+ *     E = (q.x - p.x) * (py - p.y) - (q.y - p.y) * (px - p.x)
+ * in float64, every operation rounded on its own; E is negated when u was not the lower one.  Both
+ * faces of a shared edge see the same magnitude with opposite signs: a pixel near a shared edge
+ * cannot be rejected by both.
+ * Face (a, b, c): area2 = (b.x - a.x) * (c.y - a.y) - (b.y - a.y) * (c.x - a.x).  area2 == 0 (or
+ * NaN): the face contains nothing.  area2 > 0: it contains the pixel iff E(a->b), E(b->c), E(c->a)
+ * are all >= 0; area2 < 0: iff all three are <= 0.  A pixel contained in several faces (on an
+ * edge, at a vertex, in overlapping faces) takes the LOWEST face index.
+ *     pixel_rows[j][i] = face_row[f] of that face, or -1 when no face contains the pixel.
+ *
+ * msw_raster_create copies the geometry, builds on the host a uniform bucket grid over the mesh
+ * (face indices per bucket, ascending; a face is listed in every bucket its bounding box, widened
+ * by a rounding margin, touches), uploads it, runs the locate kernel on `stream` and waits for
+ * it: on return pixel_rows is complete and the handle may be used on any stream.  The handle owns
+ * its device memory; calls that share a handle need no ordering among themselves (they only read).
+ * MSW_ERR_INVALID, with nothing allocated: NULLs (face_row may be NULL), negative counts, a
+ * non-finite coordinate or grid number, dx or dy zero, width or height < 1, width * height >
+ * 2^31 - 1, a vertex index outside [0, num_nodes), a face_row below -1, device < 0.
+ * MSW_ERR_UNSUPPORTED: more than 2^26 faces. */
+typedef struct {
+  double  x0, y0;         /* centre of pixel (0, 0)                                                 */
+  double  dx, dy;         /* pixel pitch, != 0, either sign                                          */
+  int32_t width, height;  /* >= 1, width * height <= 2^31 - 1                                        */
+} msw_raster_grid;
+
+typedef struct {
+  int64_t buckets;            /* buckets of the host-built grid (buckets_x * buckets_y)             */
+  int64_t list_entries;       /* face indices over all bucket lists                                 */
+  int64_t longest_list;       /* faces in the longest bucket list                                   */
+  int64_t device_bytes;       /* device memory the handle owns                                      */
+  double  host_build_seconds; /* host time of the checks, the face records and the bucket grid      */
+  double  locate_us;          /* device time of the locate kernel (events around it, at create)     */
+  int32_t buckets_x, buckets_y;
+} msw_raster_stats;
+
+typedef struct msw_raster msw_raster;
+int msw_raster_create(const double* node_xy, int64_t num_nodes, const int32_t* face_nodes,
+                      const int32_t* face_row, int64_t num_faces, const msw_raster_grid* grid,
+                      int device, void* stream, msw_raster** out);
+int msw_raster_destroy(msw_raster* raster);
+/* *pixel_rows = the handle's device array int32 [height][width]; it lives as long as the handle. */
+int msw_raster_pixel_rows(const msw_raster* raster, const int32_t** pixel_rows);
+int msw_raster_get_stats(const msw_raster* raster, msw_raster_stats* stats);
+
+/* out[l][j][i] = the 32-bit word layers[l * layer_stride + row_offset + pixel_rows[j][i]], or the
+ * word nodata_bits where pixel_rows is -1.  layers (device, float32 or int32 alike: words are
+ * copied as bits, NaN payloads and -0.0 survive) holds num_rows words per layer that may be
+ * addressed; out is device [num_layers][height][width].  row_offset lets one handle serve every
+ * member of an ensemble batch and every simulation on the same mesh.  Stream-ordered, no host
+ * synchronisation, no allocation.  num_layers = 0: no-op.
+ * MSW_ERR_INVALID (before any HIP call): NULL raster, layers or out, negative num_layers,
+ * layer_stride or num_rows, a face_row of the handle for which row_offset + face_row lies outside
+ * [0, num_rows) (checked against the smallest and the largest face_row >= 0). */
+int msw_raster_sample(const msw_raster* raster, const void* layers, int32_t num_layers,
+                      int64_t layer_stride, int64_t row_offset, int64_t num_rows,
+                      uint32_t nodata_bits, void* out, void* stream);
+/* Frames of a rollout pred (device float32 [N][2][T], graph numbering):
+ *     out[k][j][i] = pred[row_offset + pixel_rows[j][i]][var][t_begin + k],  k < t_count,
+ * or nodata_bits; out is device, frame-major [t_count][height][width].  A row's steps are fetched
+ * with 16-byte loads where pred, T and t_begin are multiples of 16 bytes / 4 steps.  Stream-ordered,
+ * no host synchronisation, no allocation.  t_count = 0: no-op.
+ * MSW_ERR_INVALID (before any HIP call): NULL raster, pred or out, var not 0 or 1, negative N or T,
+ * a window outside [0, T], a face_row for which row_offset + face_row lies outside [0, N). */
+int msw_raster_frames(const msw_raster* raster, const float* pred, int64_t N, int32_t T, int32_t var,
+                      int32_t t_begin, int32_t t_count, int64_t row_offset, uint32_t nodata_bits,
+                      void* out, void* stream);
+/* The launch of the locate kernel for a width x height grid (from the code the launcher itself
+ * uses): one-wave workgroups, each taking one 8 x 8 pixel block (pixels_per_wg = 64, blocks in
+ * row-major order, ragged at the right and bottom rims) per round of its loop, so that
+ * grid * iters >= ceil(width / 8) * ceil(height / 8).  msw_raster_sample and msw_raster_frames walk
+ * rounds of 64 consecutive pixels under the same cap of 4096 workgroups.
+ * MSW_ERR_INVALID: a NULL output, width or height < 1, too many pixels.  Host only. */
+int msw_raster_launch(int32_t width, int32_t height, int32_t* grid, int32_t* pixels_per_wg,
+                      int32_t* iters);
+
 /* ---- Training: autograd through one SWEGNN processor ------------------------
  * Replaces the autograd of SWEGNN.forward (models/gnn.py:387-445) the reference trains through
  * in training_step (training/train.py:125-145).  Stateless: every buffer is device memory the

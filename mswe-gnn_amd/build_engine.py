@@ -19,7 +19,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 SRC = ["csrc/kernels_nt1.hip", "csrc/kernels_nt2.hip", "csrc/kernels_nt4.hip",
        "csrc/kernels_common.hip", "csrc/plan.hip", "csrc/metrics.hip", "csrc/floodmaps.hip", "csrc/series.hip",
-       "csrc/train.hip", "csrc/loss.hip", "csrc/ensemble.hip", "csrc/scores.hip"]
+       "csrc/train.hip", "csrc/loss.hip", "csrc/ensemble.hip", "csrc/scores.hip", "csrc/raster.hip"]
 HDR = ["csrc/engine.h", "csrc/kernels_impl.h", "csrc/tiling.h", "csrc/graph_build.h", os.path.join(ROOT, "include", "mswegnn.h")]
 HDR += sorted(os.path.join("csrc", "kernels", f) for f in os.listdir(os.path.join(HERE, "csrc", "kernels")) if f.endswith(".h"))
 ARCH = os.environ.get("MSW_OFFLOAD_ARCH", "gfx950")

@@ -1478,6 +1478,8 @@ int64_t msw_struct_size(const char* name) {
   if (!strcmp(name, "msw_ensemble_steps_out")) return sizeof(msw_ensemble_steps_out);
   if (!strcmp(name, "msw_ensemble_maps_out")) return sizeof(msw_ensemble_maps_out);
   if (!strcmp(name, "msw_ensemble_scores_out")) return sizeof(msw_ensemble_scores_out);
+  if (!strcmp(name, "msw_raster_grid")) return sizeof(msw_raster_grid);
+  if (!strcmp(name, "msw_raster_stats")) return sizeof(msw_raster_stats);
   return -1;
 }
 

@@ -7,7 +7,8 @@ binding (``_lib``), plans (``engine``), the rollout-path operators and the fused
 ``rollout_test`` (``rollout``), batching (``batch``), partitioning (``partition``),
 on-device metrics (``metrics``), on-device flood maps and chunked rollouts (``floodmaps``), on-device
 zone series (``series``), on-device ensemble products and the
-scores of an ensemble against a truth run (``ensemble``), the training layers'
+scores of an ensemble against a truth run (``ensemble``), maps and rollout frames resampled
+onto regular grids (``raster``), the training layers'
 autograd (``autograd``), the training loss (``loss``) and the synthetic meshes (``mesh``).
 """
 import os

@@ -143,6 +143,17 @@ class MswEnsembleScoresOut(C.Structure):
     _fields_ = [("sums", C.c_void_p), ("reliability", C.c_void_p), ("cell_crps", C.c_void_p)]
 
 
+class MswRasterGrid(C.Structure):
+    _fields_ = [("x0", C.c_double), ("y0", C.c_double), ("dx", C.c_double), ("dy", C.c_double),
+                ("width", C.c_int32), ("height", C.c_int32)]
+
+
+class MswRasterStats(C.Structure):
+    _fields_ = [("buckets", C.c_int64), ("list_entries", C.c_int64), ("longest_list", C.c_int64),
+                ("device_bytes", C.c_int64), ("host_build_seconds", C.c_double), ("locate_us", C.c_double),
+                ("buckets_x", C.c_int32), ("buckets_y", C.c_int32)]
+
+
 MAX_LOSS_RANGES = 64
 TRAIN_LOSS_RECORD = 12
 LOSS_TYPE = {"RMSE": 0, "MAE": 1}
@@ -203,6 +214,16 @@ SYMBOLS = [
                                              C.c_int32, C.c_int32, C.c_int32, C.POINTER(MswEnsembleScoresOut),
                                              C.c_void_p]),
     ("msw_ensemble_scores_launch", C.c_int, [C.c_int64, C.c_int32, C.c_int32, c_int32_p, c_int32_p, c_int32_p]),
+    ("msw_raster_create", C.c_int, [C.POINTER(C.c_double), C.c_int64, c_int32_p, c_int32_p, C.c_int64,
+                                    C.POINTER(MswRasterGrid), C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
+    ("msw_raster_destroy", C.c_int, [C.c_void_p]),
+    ("msw_raster_pixel_rows", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    ("msw_raster_get_stats", C.c_int, [C.c_void_p, C.POINTER(MswRasterStats)]),
+    ("msw_raster_sample", C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64,
+                                    C.c_uint32, C.c_void_p, C.c_void_p]),
+    ("msw_raster_frames", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                    C.c_int32, C.c_int64, C.c_uint32, C.c_void_p, C.c_void_p]),
+    ("msw_raster_launch", C.c_int, [C.c_int32, C.c_int32, c_int32_p, c_int32_p, c_int32_p]),
     ("msw_plan_create_part", C.c_int, [C.POINTER(MswGraphDesc), C.POINTER(MswModelDesc), C.c_int,
                                        C.POINTER(MswExchangeDesc), C.c_int32, C.POINTER(C.c_void_p)]),
     ("msw_comm_unique_id", C.c_int, [C.c_char_p]),
@@ -241,7 +262,8 @@ STRUCTS = {"msw_linear": MswLinear, "msw_mlp": MswMlp, "msw_swegnn": MswSwegnn,
            "msw_flood_maps": MswFloodMaps, "msw_zone_series": MswZoneSeries,
            "msw_train_loss_desc": MswTrainLossDesc,
            "msw_ensemble_steps_out": MswEnsembleStepsOut, "msw_ensemble_maps_out": MswEnsembleMapsOut,
-           "msw_ensemble_scores_out": MswEnsembleScoresOut}
+           "msw_ensemble_scores_out": MswEnsembleScoresOut,
+           "msw_raster_grid": MswRasterGrid, "msw_raster_stats": MswRasterStats}
 
 _lib = None
 

@@ -29,7 +29,7 @@ import numpy as np
 import torch
 
 __all__ = ["Graph", "make_multiscale_mesh", "make_single_scale_mesh", "wet_state",
-           "mesh_config", "config3_members", "irregularize"]
+           "mesh_config", "config3_members", "irregularize", "multiscale_geometry"]
 
 
 class Graph:
@@ -269,6 +269,22 @@ def make_multiscale_mesh(n_coarse=3, num_scales=4, seed=0, T=48, previous_t=3,
         area=torch.from_numpy(np.concatenate([sc["area"] for sc in scales]).astype(np.float32)),
         edge_BC_length=torch.tensor([sc["bc_edge_len"] for sc in scales], dtype=torch.float32),
     )
+
+
+def multiscale_geometry(n_coarse=3, num_scales=4, seed=0, jitter=0.25, size=1000.0):
+    """The triangulation behind ``make_multiscale_mesh(n_coarse, num_scales, seed, jitter=...,
+    size=...)``: per scale, finest first, ``(node_xy float64 [V, 2], face_nodes int32 [nf, 3])``
+    (``mswegnn.raster`` resamples per-cell maps through it).  Face f of scale s is graph row
+    ``node_ptr[s] + f``; the ghost row of a scale has no face.  The generator's first draws are
+    the coarse jitter, so a fresh ``default_rng(seed)`` reproduces the vertices."""
+    rng = np.random.default_rng(seed)
+    xy, tris = _coarse_triangulation(n_coarse, rng, jitter, size)
+    levels = [(xy, tris)]
+    for _ in range(num_scales - 1):
+        xy, tris, _ = _refine(*levels[-1])
+        levels.append((xy, tris))
+    return [(np.ascontiguousarray(xy, dtype=np.float64), np.ascontiguousarray(tris, dtype=np.int32))
+            for xy, tris in levels[::-1]]
 
 
 def make_single_scale_mesh(n_coarse=3, refinements=3, seed=0, T=10, previous_t=3, **kw):
