@@ -594,6 +594,89 @@ int msw_raster_frames(const msw_raster* raster, const float* pred, int64_t N, in
 int msw_raster_launch(int32_t width, int32_t height, int32_t* grid, int32_t* pixels_per_wg,
                       int32_t* iters);
 
+/* Zonal statistics: raster layers and frame stacks reduced onto the cells of one mesh scale, the
+ * transpose of the raster products -- a DEM, a roughness layer, an observed depth raster or the
+ * frames of a raster model become per-cell values and [N][2][T] rows.  Centres only, as above: a
+ * pixel belongs to the face that pixel_rows names for it, whole.  The reference has no counterpart.
+ *
+ * msw_zonal_create builds on the device, from a raster handle, and owns
+ *   face_ptr     int32 [num_faces + 1], pixels int32 [face_ptr[num_faces]]: the list of face f,
+ *                pixels[face_ptr[f] .. face_ptr[f + 1]), holds exactly the pixel indices
+ *                p = j * width + i with pixel_rows[p] == face_row[f], ascending; empty for a face
+ *                with face_row -1 and for a zero-area face.  The lists together are a permutation
+ *                of {p : pixel_rows[p] >= 0}.
+ *   centre_pixel int32 [num_faces]: the pixel nearest to the face's centroid, in float64, every
+ *                operation rounded on its own: cx = ((a.x + b.x) + c.x) / 3.0 (cy likewise),
+ *                i = floor((cx - x0) / dx + 0.5), j = floor((cy - y0) / dy + 0.5); j * width + i
+ *                when 0 <= i < width and 0 <= j < height, else -1.
+ * The handle copies what it needs: it outlives the raster handle, and calls that share it need no
+ * ordering among themselves (they only read).  Create runs on `stream` and waits for it.
+ * MSW_ERR_INVALID: a NULL argument.  MSW_ERR_UNSUPPORTED: two faces with the same face_row >= 0
+ * (the lists are keyed by face; such a mesh would count pixels twice).  A refusal leaves nothing
+ * allocated. */
+typedef struct {
+  int64_t num_faces;
+  int64_t listed_pixels;  /* face_ptr[num_faces]                                                   */
+  int64_t longest_list;   /* pixels in the longest list                                            */
+  int64_t empty_faces;    /* faces with face_row >= 0 and an empty list                            */
+  int64_t wave_faces;     /* faces with more than 32 pixels: msw_zonal_reduce's second launch      */
+  int64_t device_bytes;   /* device memory the handle owns                                         */
+  double  build_us;       /* host clock around create: kernels, copies and the host prefix sum     */
+} msw_zonal_stats;
+
+typedef struct msw_zonal msw_zonal;
+int msw_zonal_create(const msw_raster* raster, void* stream, msw_zonal** out);
+int msw_zonal_destroy(msw_zonal* zonal);
+/* The handle's device arrays; they live as long as the handle. */
+int msw_zonal_lists(const msw_zonal* zonal, const int32_t** face_ptr, const int32_t** pixels,
+                    const int32_t** centre_pixel);
+int msw_zonal_get_stats(const msw_zonal* zonal, msw_zonal_stats* stats);
+
+/* Per-cell statistics of layers (device float32 [num_layers][height][width], layer l at
+ * layers + l * layer_stride).  Four outputs, each device [num_layers][out_stride] or NULL: mean
+ * and vmin / vmax float32, count int32.  Face f with r = face_row[f] >= 0 writes element
+ * l * out_stride + row_offset + r of every output given; every other element is left untouched,
+ * so one call per scale fills one [N] array of a multiscale graph.  Per face and layer:
+ *   a pixel whose value is NaN is skipped; count = the pixels not skipped;
+ *   mean = (float)(S / (double)count), S the float64 sum of the remaining values started from
+ *   +0.0 (a cell of -0.0 pixels has mean +0.0).  The order of the sum is a function of the list
+ *   alone (not of the layer count, offsets, stream or repetition): a list of n <= 32 entries is
+ *   summed front to back; a longer one as 64 partial sums, partial k over the entries k, k + 64,
+ *   k + 128, ... front to back from +0.0, which are then combined pairwise: s[k] + s[k ^ 32], then
+ *   ^ 16, ^ 8, ^ 4, ^ 2, ^ 1;
+ *   vmin / vmax = one pixel's own word, copied as bits, the least / greatest by IEEE comparison
+ *   with -0.0 below +0.0 (no dependence on order);
+ *   count == 0: with fill_centre != 0 and centre_pixel[f] >= 0, mean, vmin and vmax take that
+ *   pixel's word of the layer, copied as bits (a NaN included); otherwise nodata_bits.  count stays 0.
+ * Stream-ordered, no host synchronisation, no allocation.  num_layers = 0: no-op.
+ * MSW_ERR_INVALID (before any HIP call): NULL zonal or layers, all four outputs NULL, negative
+ * num_layers, layer_stride, num_rows or out_stride, a face_row for which row_offset + face_row
+ * lies outside [0, num_rows). */
+int msw_zonal_reduce(const msw_zonal* zonal, const float* layers, int32_t num_layers,
+                     int64_t layer_stride, int64_t row_offset, int64_t num_rows, int64_t out_stride,
+                     int32_t fill_centre, uint32_t nodata_bits, float* mean, int32_t* count,
+                     float* vmin, float* vmax, void* stream);
+/* The inverse of msw_raster_frames: frames (device float32 [t_count][height][width], frame k at
+ * frames + k * frame_stride) into a rollout array pred (device float32 [N][2][T]):
+ *     pred[row_offset + face_row[f]][var][t_begin + k] = the mean msw_zonal_reduce gives for
+ * frame k and face f, bit for bit (the same device function), fill_centre and nodata_bits
+ * included.  Nothing else in pred is touched.  Stream-ordered, no host synchronisation, no
+ * allocation.  t_count = 0: no-op.
+ * MSW_ERR_INVALID (before any HIP call): NULL zonal, frames or pred, var not 0 or 1, negative N, T
+ * or frame_stride, a window outside [0, T], a face_row for which row_offset + face_row lies
+ * outside [0, N). */
+int msw_zonal_frames(const msw_zonal* zonal, const float* frames, int64_t frame_stride, float* pred,
+                     int64_t N, int32_t T, int32_t var, int32_t t_begin, int32_t t_count,
+                     int64_t row_offset, int32_t fill_centre, uint32_t nodata_bits, void* stream);
+/* The launch of the reduce kernel over num_faces faces (from the code the launcher itself uses):
+ * one-wave workgroups, each taking faces_per_wg = 64 consecutive faces per round of its loop, so
+ * that grid * 64 * iters >= num_faces; a lane reduces the list of its face when it holds at most
+ * 32 pixels.  The wave_faces faces with longer lists go to a second launch, one face per wave and
+ * round, of min(wave_faces, the same cap of 4096) workgroups; a launch with no face to take is not
+ * made.  num_faces = 0: grid and iters are 0.
+ * MSW_ERR_INVALID: a NULL output, num_faces negative.  Host only. */
+int msw_zonal_launch(int64_t num_faces, int32_t* grid, int32_t* faces_per_wg, int32_t* iters);
+
 /* ---- Training: autograd through one SWEGNN processor ------------------------
  * Replaces the autograd of SWEGNN.forward (models/gnn.py:387-445) the reference trains through
  * in training_step (training/train.py:125-145).  Stateless: every buffer is device memory the

@@ -19,8 +19,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 SRC = ["csrc/kernels_nt1.hip", "csrc/kernels_nt2.hip", "csrc/kernels_nt4.hip",
        "csrc/kernels_common.hip", "csrc/plan.hip", "csrc/metrics.hip", "csrc/floodmaps.hip", "csrc/series.hip",
-       "csrc/train.hip", "csrc/loss.hip", "csrc/ensemble.hip", "csrc/scores.hip", "csrc/raster.hip"]
-HDR = ["csrc/engine.h", "csrc/kernels_impl.h", "csrc/tiling.h", "csrc/graph_build.h", os.path.join(ROOT, "include", "mswegnn.h")]
+       "csrc/train.hip", "csrc/loss.hip", "csrc/ensemble.hip", "csrc/scores.hip", "csrc/raster.hip",
+       "csrc/zonal.hip"]
+HDR = ["csrc/engine.h", "csrc/kernels_impl.h", "csrc/tiling.h", "csrc/graph_build.h", "csrc/raster_handle.h",
+       os.path.join(ROOT, "include", "mswegnn.h")]
 HDR += sorted(os.path.join("csrc", "kernels", f) for f in os.listdir(os.path.join(HERE, "csrc", "kernels")) if f.endswith(".h"))
 ARCH = os.environ.get("MSW_OFFLOAD_ARCH", "gfx950")
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-result",
@@ -69,7 +71,11 @@ def build(force=False, verbose=True, variant=""):
              "nostream": ["-DMSW_STREAM_ST=0"],
              # kernel arguments fetched where they are first used instead of pinned at kernel
              # entry (kernels/k_base.h MSW_PIN): tests/test_gpu_args_hoist.py
-             "lazyargs": ["-DMSW_ARGS_HOIST=0"]}.get(variant, [])
+             "lazyargs": ["-DMSW_ARGS_HOIST=0"],
+             # the zonal reduce with one mapping for every list, a lane or the wave, in place of
+             # the choice by list length (csrc/zonal.hip kSerial): tools/zonal_bench.py --mappings
+             "zonallane": ["-DMSW_ZONAL_SERIAL=2147483647"],
+             "zonalwave": ["-DMSW_ZONAL_SERIAL=0"]}.get(variant, [])
     os.makedirs(odir, exist_ok=True)
     os.makedirs(os.path.join(HERE, "lib"), exist_ok=True)
     out = lib_path(variant)

@@ -1480,6 +1480,7 @@ int64_t msw_struct_size(const char* name) {
   if (!strcmp(name, "msw_ensemble_scores_out")) return sizeof(msw_ensemble_scores_out);
   if (!strcmp(name, "msw_raster_grid")) return sizeof(msw_raster_grid);
   if (!strcmp(name, "msw_raster_stats")) return sizeof(msw_raster_stats);
+  if (!strcmp(name, "msw_zonal_stats")) return sizeof(msw_zonal_stats);
   return -1;
 }
 

@@ -30,6 +30,7 @@
 
 #include "../../include/mswegnn.h"
 #include "engine.h"
+#include "raster_handle.h"
 
 // Every operation rounds on its own, as written (host and device): the edge functions, area2, the
 // pixel centres and bucket_of are restated operation for operation by the tests.
@@ -43,16 +44,7 @@ constexpr int kBlock = 8;       // a wave is a kBlock x kBlock pixel block
 constexpr int64_t kMaxFaces = (int64_t)1 << 26;
 constexpr int kMaxBucketsPerAxis = 8192;
 
-constexpr int kNegAB = 1, kNegBC = 2, kNegCA = 4;  // FaceRec::flags: the edge's first vertex is not the lower one
-constexpr int kAreaPos = 16;                       // area2 > 0 (listed faces have area2 != 0)
-
-struct alignas(64) FaceRec {
-  double ax, ay, bx, by, cx, cy;
-  int32_t flags;
-  int32_t row;
-  double pad;
-};
-static_assert(sizeof(FaceRec) == 64, "one 64-byte record per face");
+using namespace msw_raster_detail;  // FaceRec, its flags, face_margin (raster_handle.h)
 
 // The bucket grid: [gx0, gx1] x [gy0, gy1] cut into nbx x nby buckets.
 struct Buckets {
@@ -210,18 +202,6 @@ int check_grid(int32_t W, int32_t H) {
   return MSW_OK;
 }
 
-// How far outside a face's bounding box a pixel that the fp64 predicates accept can lie.  An edge
-// function is L * (distance to the edge's line) with a rounding error below 8 eps L D (D the
-// larger side of the bounding box, L <= sqrt(2) D an edge, eps = 2^-53: the differences are taken
-// first, so the error scales with the face, not with the size of the coordinates); three lines
-// each off by 8 eps D move a corner of angle theta by that over sin(theta / 2) <= 2 D / h, h =
-// |area2| / L the smallest altitude: below 2^-47 D^3 / |area2|.  2^-40 leaves a factor of 100.
-// Capped at D: a face thinner than 2^-40 of its length is listed as if it were twice as large.
-double face_margin(double D, double area2) {
-  const double m = 0x1p-40 * D * (D * D / std::fabs(area2));
-  return m <= D ? m : D;  // also a NaN or infinite m
-}
-
 // The host side of msw_raster_create after its checks: the face records and the bucket CSR.
 struct HostBuild {
   std::vector<FaceRec> rec;
@@ -325,17 +305,6 @@ int build_host(const double* node_xy, const int32_t* face_nodes, const int32_t* 
 
 }  // namespace
 
-struct msw_raster {
-  int device = -1;
-  msw_raster_grid g{};
-  int32_t min_row = 0, max_row = -1;  // over face_row >= 0 (max_row -1: no face has a value)
-  FaceRec* d_rec = nullptr;
-  int32_t* d_bptr = nullptr;
-  int32_t* d_bface = nullptr;
-  int32_t* d_prow = nullptr;
-  msw_raster_stats stats{};
-};
-
 namespace {
 
 void release(msw_raster* r) {
@@ -401,6 +370,7 @@ extern "C" int msw_raster_create(const double* node_xy, int64_t num_nodes, const
   msw_raster* rs = new msw_raster;
   rs->device = device;
   rs->g = g;
+  rs->num_faces = num_faces;
   rs->min_row = hb.min_row;
   rs->max_row = hb.max_row;
   rs->stats.buckets = (int64_t)b.nbx * b.nby;

@@ -154,6 +154,12 @@ class MswRasterStats(C.Structure):
                 ("buckets_x", C.c_int32), ("buckets_y", C.c_int32)]
 
 
+class MswZonalStats(C.Structure):
+    _fields_ = [("num_faces", C.c_int64), ("listed_pixels", C.c_int64), ("longest_list", C.c_int64),
+                ("empty_faces", C.c_int64), ("wave_faces", C.c_int64), ("device_bytes", C.c_int64),
+                ("build_us", C.c_double)]
+
+
 MAX_LOSS_RANGES = 64
 TRAIN_LOSS_RECORD = 12
 LOSS_TYPE = {"RMSE": 0, "MAE": 1}
@@ -224,6 +230,16 @@ SYMBOLS = [
     ("msw_raster_frames", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
                                     C.c_int32, C.c_int64, C.c_uint32, C.c_void_p, C.c_void_p]),
     ("msw_raster_launch", C.c_int, [C.c_int32, C.c_int32, c_int32_p, c_int32_p, c_int32_p]),
+    ("msw_zonal_create", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    ("msw_zonal_destroy", C.c_int, [C.c_void_p]),
+    ("msw_zonal_lists", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    ("msw_zonal_get_stats", C.c_int, [C.c_void_p, C.POINTER(MswZonalStats)]),
+    ("msw_zonal_reduce", C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                                   C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p]),
+    ("msw_zonal_frames", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
+                                   C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_uint32, C.c_void_p]),
+    ("msw_zonal_launch", C.c_int, [C.c_int64, c_int32_p, c_int32_p, c_int32_p]),
     ("msw_plan_create_part", C.c_int, [C.POINTER(MswGraphDesc), C.POINTER(MswModelDesc), C.c_int,
                                        C.POINTER(MswExchangeDesc), C.c_int32, C.POINTER(C.c_void_p)]),
     ("msw_comm_unique_id", C.c_int, [C.c_char_p]),
@@ -263,7 +279,8 @@ STRUCTS = {"msw_linear": MswLinear, "msw_mlp": MswMlp, "msw_swegnn": MswSwegnn,
            "msw_train_loss_desc": MswTrainLossDesc,
            "msw_ensemble_steps_out": MswEnsembleStepsOut, "msw_ensemble_maps_out": MswEnsembleMapsOut,
            "msw_ensemble_scores_out": MswEnsembleScoresOut,
-           "msw_raster_grid": MswRasterGrid, "msw_raster_stats": MswRasterStats}
+           "msw_raster_grid": MswRasterGrid, "msw_raster_stats": MswRasterStats,
+           "msw_zonal_stats": MswZonalStats}
 
 _lib = None
 

@@ -16,8 +16,16 @@ The containing cell's value is the product -- cell values are finite-volume mean
 interpolation, no supersampling and no area coverage; triangles only; no file formats or coordinate
 reference systems; masking dry pixels is one ``torch.where`` on the raster.
 
+The other way -- a DEM, a roughness layer, an observed depth raster, the frame stack of a raster
+model onto the cells -- is :meth:`Rasterizer.cells`: a :class:`CellPixels` holds, for every face,
+the pixels whose centre it contains (C ABI ``msw_zonal_*``, the transpose of ``pixel_rows``) and
+reduces rasters over them: :meth:`CellPixels.reduce` (mean, count, min, max per cell, the mean from
+a float64 sum in an order that depends on the cell's list alone) and
+:meth:`CellPixels.frames_to_rows`, the exact inverse of :meth:`Rasterizer.frames`.
+
 On CPU tensors the same interface runs :func:`_locate_torch` / :func:`_sample_torch` /
-:func:`_frames_torch`, plain numpy / torch restatements.
+:func:`_frames_torch` / :func:`_cells_torch` / :func:`_reduce_torch`, plain numpy / torch
+restatements.
 """
 from __future__ import annotations
 
@@ -30,7 +38,7 @@ import torch
 
 from . import _lib as L
 
-__all__ = ["RasterGrid", "Rasterizer", "raster_launch"]
+__all__ = ["RasterGrid", "Rasterizer", "CellPixels", "raster_launch", "zonal_launch"]
 
 _MAX_PIXELS = 2 ** 31 - 1
 
@@ -213,6 +221,7 @@ class Rasterizer:
         self.max_row = int(valued.max()) if valued.size else -1
         self.grid, self.device = grid, torch.device(device)
         self.num_faces = nf
+        self._geometry = (xy, fn, fr)  # what cells() needs: the centre pixels, the rows of the faces
         self._handle, self._rows = None, None
         if self.device.type == "cuda":
             index = torch.cuda.current_device() if self.device.index is None else self.device.index
@@ -315,6 +324,13 @@ class Rasterizer:
                                               self._stream(stream)))
         return out
 
+    def cells(self, stream=None):
+        """The transpose of ``pixel_rows``: a :class:`CellPixels` with every face's pixel list, for
+        reducing rasters onto the cells.  It copies what it needs and outlives this rasterizer."""
+        if self._handle is None and self._rows is None:
+            raise RuntimeError("the rasterizer is closed")
+        return CellPixels(self, stream)
+
     # ------------------------------------------------------------------ bookkeeping
     def launch(self):
         """``(grid, pixels_per_wg, iters)`` of the locate kernel for this grid."""
@@ -334,6 +350,286 @@ class Rasterizer:
         if handle is not None:
             L.lib().msw_raster_destroy(handle)
             self._rows = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # interpreter shutdown
+            pass
+
+
+# ---------------------------------------------------------------------- raster -> mesh
+def zonal_launch(num_faces):
+    """``(grid, faces_per_wg, iters)`` of the reduce kernel over ``num_faces`` faces (host only)."""
+    g, p, it = C.c_int32(), C.c_int32(), C.c_int32()
+    L.check(L.lib().msw_zonal_launch(int(num_faces), C.byref(g), C.byref(p), C.byref(it)))
+    return g.value, p.value, it.value
+
+
+def _cells_torch(pixel_rows, node_xy, face_nodes, face_row, grid):
+    """``(face_ptr [nf + 1], pixels, centre_pixel [nf])`` int32 in numpy: the lists from a stable
+    argsort of ``pixel_rows`` (ascending pixel index within a row), the centre pixel operation for
+    operation in float64.  No two faces share a row (the caller has checked)."""
+    rows = pixel_rows.reshape(-1).numpy()
+    nf = face_row.shape[0]
+    order = np.argsort(rows, kind="stable")
+    order = order[rows[order] >= 0].astype(np.int32)
+    valued = face_row >= 0
+    top = int(face_row.max()) + 1 if valued.any() else 0
+    per_row = np.bincount(rows[rows >= 0], minlength=top)[:top] if top else np.zeros(0, np.int64)
+    # a pixel_rows value beyond the faces' rows cannot occur: pixel_rows holds face_row values only
+    row_start = np.concatenate([[0], np.cumsum(per_row)])
+    n = np.zeros(nf, np.int64)
+    n[valued] = per_row[face_row[valued]]
+    face_ptr = np.concatenate([[0], np.cumsum(n)])
+    src = np.repeat(row_start[np.where(valued, face_row, 0)] - face_ptr[:-1], n) + np.arange(face_ptr[-1])
+    pixels = order[src]
+    xy = node_xy[face_nodes]                                   # [nf, 3, 2]
+    cx = ((xy[:, 0, 0] + xy[:, 1, 0]) + xy[:, 2, 0]) / 3.0
+    cy = ((xy[:, 0, 1] + xy[:, 1, 1]) + xy[:, 2, 1]) / 3.0
+    with np.errstate(over="ignore", invalid="ignore"):
+        i = np.floor((cx - grid.x0) / grid.dx + 0.5)
+        j = np.floor((cy - grid.y0) / grid.dy + 0.5)
+    inside = (i >= 0) & (i < grid.width) & (j >= 0) & (j < grid.height)
+    centre = np.where(inside, np.where(inside, j, 0) * grid.width + np.where(inside, i, 0), -1).astype(np.int32)
+    return (torch.from_numpy(face_ptr.astype(np.int32)), torch.from_numpy(np.ascontiguousarray(pixels, np.int32)),
+            torch.from_numpy(centre))
+
+
+def _reduce_torch(face_ptr, pixels, centre, layers, fill_centre, nodata_word):
+    """Per-face words ``mean``, ``count``, ``min``, ``max`` [L, nf] int32 of ``layers`` [L, P]
+    float32 from plain torch ops: float64 ``index_add_`` sums (sequential on the CPU), the extremes
+    through an integer key in IEEE order with -0.0 below +0.0."""
+    words = layers.contiguous().view(torch.int32)
+    nl, nf = layers.shape[0], centre.shape[0]
+    n = (face_ptr[1:] - face_ptr[:-1]).long()
+    seg = torch.repeat_interleave(torch.arange(nf), n)
+    pw = words[:, pixels.long()]
+    pv = pw.view(torch.float32)
+    ok = ~torch.isnan(pv)
+    total = torch.zeros(nl, nf, dtype=torch.float64).index_add_(1, seg, torch.where(ok, pv, torch.zeros(())).double())
+    count = torch.zeros(nl, nf, dtype=torch.int64).index_add_(1, seg, ok.long())
+    b = pw.long()
+    key = torch.where(b >= 0, b, -(b & 0x7FFFFFFF) - 1)
+    big = torch.tensor(1 << 40)
+    segs = seg.expand(nl, -1)
+    lo = torch.full((nl, nf), 1 << 40).scatter_reduce(1, segs, torch.where(ok, key, big), "amin")
+    hi = torch.full((nl, nf), -(1 << 40)).scatter_reduce(1, segs, torch.where(ok, key, -big), "amax")
+
+    def word(k):
+        w = torch.where(k >= 0, k, (-(k + 1)) | 0x80000000)
+        return (((w + (1 << 31)) % (1 << 32)) - (1 << 31)).to(torch.int32)
+    fill = torch.full((nl, nf), nodata_word, dtype=torch.int32)
+    if fill_centre:
+        fill = torch.where(centre >= 0, words[:, centre.long().clamp(min=0)], fill)
+    have = count > 0
+    mean = (total / count.clamp(min=1).double()).float().view(torch.int32)
+    return {"mean": torch.where(have, mean, fill), "count": count.to(torch.int32),
+            "min": torch.where(have, word(lo), fill), "max": torch.where(have, word(hi), fill)}
+
+
+_OUTPUTS = ("mean", "count", "min", "max")
+
+
+class CellPixels:
+    """For every face of a :class:`Rasterizer` the pixels whose centre it contains (C ABI
+    ``msw_zonal_*``), and reductions of rasters over them: :meth:`reduce` / :meth:`mean` for layers
+    (a DEM, roughness, an observed depth), :meth:`frames_to_rows` for a frame stack into
+    ``[N, 2, T]`` rows -- the inverse of :meth:`Rasterizer.frames`.  Centres only: no fractional
+    coverage.  Made by :meth:`Rasterizer.cells`; two faces with the same row are refused."""
+
+    def __init__(self, raster, stream=None):
+        xy, fn, fr = raster._geometry
+        valued = fr[fr >= 0]
+        if np.unique(valued).size != valued.size:
+            raise ValueError("two faces share a face_row: the lists are keyed by face")
+        self.grid, self.device = raster.grid, raster.device
+        self.num_faces, self.min_row, self.max_row = raster.num_faces, raster.min_row, raster.max_row
+        self._face_row = torch.from_numpy(fr)
+        self._handle, self._lists = None, None
+        if raster._handle is not None:
+            out = C.c_void_p()
+            L.check(L.lib().msw_zonal_create(raster._handle, raster._stream(stream), C.byref(out)))
+            self._handle = out
+        else:
+            self._lists = _cells_torch(raster._rows, xy, fn, fr, raster.grid)
+
+    def _stream(self, stream):
+        return C.c_void_p(stream if stream is not None else torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _get_lists(self):
+        """On a GPU: copies of the handle's arrays, made on first use."""
+        if self._lists is None:
+            if self._handle is None:
+                raise RuntimeError("the cell lists are closed")
+            ptrs = [C.c_void_p(), C.c_void_p(), C.c_void_p()]
+            L.check(L.lib().msw_zonal_lists(self._handle, *[C.byref(p) for p in ptrs]))
+            sizes = (self.num_faces + 1, self.stats()["listed_pixels"], self.num_faces)
+            copy = L.lib().hipMemcpy  # the HIP runtime the library links
+            copy.argtypes, copy.restype = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int], C.c_int
+            out = []
+            with torch.cuda.device(self.device):
+                for p, size in zip(ptrs, sizes):
+                    t = torch.empty(size, dtype=torch.int32, device=self.device)
+                    if size and copy(t.data_ptr(), p, 4 * size, 3) != 0:   # hipMemcpyDeviceToDevice
+                        raise RuntimeError("hipMemcpy failed")
+                    out.append(t)
+                torch.cuda.synchronize(self.device)
+            self._lists = tuple(out)
+        return self._lists
+
+    @property
+    def face_ptr(self):
+        """[num_faces + 1] int32: face f's list is ``pixels[face_ptr[f]:face_ptr[f + 1]]``."""
+        return self._get_lists()[0]
+
+    @property
+    def pixels(self):
+        """int32 pixel indices ``j * width + i``, ascending within a face's list."""
+        return self._get_lists()[1]
+
+    @property
+    def centre_pixel(self):
+        """[num_faces] int32: the pixel nearest to each face's centroid, -1 outside the grid."""
+        return self._get_lists()[2]
+
+    # ------------------------------------------------------------------ reductions
+    def _check(self, row_offset, num_rows):
+        if self.max_row >= 0 and not (row_offset + self.min_row >= 0 and row_offset + self.max_row < num_rows):
+            raise ValueError(f"row_offset {row_offset} + face rows [{self.min_row}, {self.max_row}] lie outside "
+                             f"the {num_rows} rows given")
+
+    def _layers(self, layers, what):
+        H, W = self.grid.shape
+        if not torch.is_tensor(layers) or layers.dim() != 3 or tuple(layers.shape[1:]) != (H, W):
+            raise ValueError(f"{what} must be [L, {H}, {W}]")
+        if layers.device != self.device:
+            raise ValueError(f"{what} are on {layers.device}, the cell lists on {self.device}")
+        if layers.dtype != torch.float32 or not layers.is_contiguous():
+            layers = layers.float().contiguous()
+        return layers
+
+    def _scatter(self, out, values, row_offset):
+        """CPU: the per-face words [L, nf] into ``out`` [L, n] at the faces' rows."""
+        valued = self._face_row >= 0
+        idx = self._face_row[valued].long() + row_offset
+        out.view(torch.int32)[:, idx] = values[:, valued]
+
+    def reduce(self, layers, row_offset=0, num_rows=None, fill_centre=True, nodata=float("nan"), out=None,
+               stream=None):
+        """Per-cell statistics of ``layers`` ``[H, W]`` or ``[L, H, W]`` -> a dict of ``mean``,
+        ``min``, ``max`` (float32) and ``count`` (int32), each ``[num_rows]`` or ``[L, num_rows]``:
+        face f's values at element ``row_offset + face_row[f]``.  NaN pixels are skipped; a cell
+        with nothing left takes the pixel nearest to its centroid (``fill_centre``) or ``nodata``,
+        its count 0.  ``out``: a dict of existing contiguous tensors (any of the four names) to
+        write into, every other element left untouched -- successive scales fill one array; without
+        it the outputs start as ``nodata`` / 0 and ``num_rows`` defaults to the rows the faces need."""
+        single = torch.is_tensor(layers) and layers.dim() == 2
+        layers = self._layers(layers[None] if single else layers, "layers")
+        nl, row_offset = layers.shape[0], int(row_offset)
+        if out is None:
+            n = row_offset + self.max_row + 1 if num_rows is None else int(num_rows)
+            self._check(row_offset, n)
+            res = {k: torch.full((nl, n), 0 if k == "count" else float(nodata),
+                                 dtype=torch.int32 if k == "count" else torch.float32, device=self.device)
+                   for k in _OUTPUTS}
+        else:
+            if not out or set(out) - set(_OUTPUTS):
+                raise ValueError(f"out holds any of {_OUTPUTS}")
+            res = {}
+            for k, t in out.items():
+                want = torch.int32 if k == "count" else torch.float32
+                if t.dtype != want or t.device != self.device or not t.is_contiguous() or t.dim() != (1 if single else 2):
+                    raise ValueError(f"out[{k!r}] must be a contiguous {want} tensor on {self.device}")
+                res[k] = t[None] if single else t
+            shapes = {tuple(t.shape) for t in res.values()}
+            n = next(iter(shapes))[1]
+            if len(shapes) != 1 or next(iter(shapes))[0] != nl or (num_rows is not None and int(num_rows) != n):
+                raise ValueError("the outputs must share one shape [L, num_rows]")
+            self._check(row_offset, n)
+        if nl and self.max_row >= 0:
+            if self._handle is None:
+                if self._lists is None:
+                    raise RuntimeError("the cell lists are closed")
+                got = _reduce_torch(*self._lists, layers.reshape(nl, -1), fill_centre, _signed(_bits(nodata)))
+                for k, t in res.items():
+                    self._scatter(t, got[k], row_offset)
+            else:
+                ptr = lambda k: C.c_void_p(res[k].data_ptr()) if k in res else None  # noqa: E731
+                L.check(L.lib().msw_zonal_reduce(self._handle, C.c_void_p(layers.data_ptr()), nl, layers.stride(0),
+                                                 row_offset, n, n, int(bool(fill_centre)), _bits(nodata), ptr("mean"),
+                                                 ptr("count"), ptr("min"), ptr("max"), self._stream(stream)))
+        return {k: (t[0] if single else t) for k, t in res.items()}
+
+    def mean(self, layers, row_offset=0, num_rows=None, fill_centre=True, nodata=float("nan"), stream=None):
+        """The mean of :meth:`reduce` alone."""
+        single = torch.is_tensor(layers) and layers.dim() == 2
+        nl = 1 if single else (layers.shape[0] if torch.is_tensor(layers) and layers.dim() == 3 else 0)
+        n = int(row_offset) + self.max_row + 1 if num_rows is None else int(num_rows)
+        if n < 0:
+            raise ValueError("num_rows negative")
+        out = torch.full((n,) if single else (nl, n), float(nodata), dtype=torch.float32, device=self.device)
+        return self.reduce(layers, row_offset, n, fill_centre, nodata, {"mean": out}, stream)["mean"]
+
+    def frames_to_rows(self, frames, pred, var=0, t_begin=0, row_offset=0, fill_centre=True, nodata=float("nan"),
+                       stream=None):
+        """Frames ``[t_count, H, W]`` into ``pred`` [N, 2, T] (float32, contiguous, written in
+        place): ``pred[row_offset + face_row[f], var, t_begin + k]`` = the :meth:`mean` of frame k
+        on face f, bit for bit; nothing else in ``pred`` changes.  Returns ``pred``."""
+        if not torch.is_tensor(pred) or pred.dim() != 3 or pred.shape[1] != 2:
+            raise ValueError("pred must be [N, 2, T]")
+        if pred.dtype != torch.float32 or not pred.is_contiguous():
+            raise ValueError("pred is written in place: it must be float32 and contiguous")
+        if var not in (0, 1):
+            raise ValueError("var is 0 (depth) or 1 (discharge)")
+        frames = self._layers(frames, "frames")
+        N, T, tc = int(pred.shape[0]), int(pred.shape[2]), int(frames.shape[0])
+        t_begin, row_offset = int(t_begin), int(row_offset)
+        if t_begin < 0 or t_begin + tc > T:
+            raise ValueError(f"steps [{t_begin}, {t_begin + tc}) lie outside the rollout's {T}")
+        if pred.device != self.device:
+            raise ValueError(f"pred is on {pred.device}, the cell lists on {self.device}")
+        self._check(row_offset, N)
+        if not tc or self.max_row < 0:
+            return pred
+        if self._handle is None:
+            if self._lists is None:
+                raise RuntimeError("the cell lists are closed")
+            got = _reduce_torch(*self._lists, frames.reshape(tc, -1), fill_centre, _signed(_bits(nodata)))["mean"]
+            valued = self._face_row >= 0
+            idx = self._face_row[valued].long() + row_offset
+            pred.view(torch.int32)[idx, var, t_begin:t_begin + tc] = got[:, valued].t()
+        else:
+            L.check(L.lib().msw_zonal_frames(self._handle, C.c_void_p(frames.data_ptr()), frames.stride(0),
+                                             C.c_void_p(pred.data_ptr()), N, T, var, t_begin, tc, row_offset,
+                                             int(bool(fill_centre)), _bits(nodata), self._stream(stream)))
+        return pred
+
+    # ------------------------------------------------------------------ bookkeeping
+    def launch(self):
+        """``(grid, faces_per_wg, iters)`` of the reduce kernel for these faces."""
+        return zonal_launch(self.num_faces)
+
+    def stats(self):
+        """``num_faces``, ``listed_pixels``, ``longest_list``, ``empty_faces`` (valued faces with an
+        empty list), ``wave_faces`` (lists of more than 32 pixels: a wave each on the GPU),
+        ``device_bytes``, ``build_us`` (the last two zero on the CPU)."""
+        s = L.MswZonalStats()
+        if self._handle is not None:
+            L.check(L.lib().msw_zonal_get_stats(self._handle, C.byref(s)))
+        elif self._lists is not None:
+            n = (self._lists[0][1:] - self._lists[0][:-1])
+            s.num_faces, s.listed_pixels = self.num_faces, int(self._lists[0][-1])
+            s.longest_list = int(n.max()) if self.num_faces else 0
+            s.empty_faces = int(((n == 0) & (self._face_row >= 0)).sum())
+            s.wave_faces = int((n > 32).sum())
+        return {k: getattr(s, k) for k, _ in L.MswZonalStats._fields_}
+
+    def close(self):
+        handle, self._handle = self._handle, None
+        self._lists = None
+        if handle is not None:
+            L.lib().msw_zonal_destroy(handle)
 
     def __del__(self):
         try:
