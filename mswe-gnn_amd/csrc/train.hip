@@ -743,7 +743,9 @@ int msw_swegnn_train_forward(const msw_swegnn_train_desc* d, const float* xs, co
                              float* saved, float* out, void* stream) {
   Layout y;
   if (!layout_of(d, y)) return set_error(MSW_ERR_INVALID, "inconsistent SWEGNN training descriptor");
-  if (!xs || !xd || !saved || !out || (d->edge_features > 0 && !ea)) return set_error(MSW_ERR_INVALID, "null argument");
+  // an empty edge_attr (no edges) has no storage: its pointer is null and nothing reads it
+  if (!xs || !xd || !saved || !out || (d->edge_features > 0 && d->num_edges > 0 && !ea))
+    return set_error(MSW_ERR_INVALID, "null argument");
   if (d->with_filter_matrix)
     for (int k = 0; k <= d->K; ++k)
       if (!d->filter[k]) return set_error(MSW_ERR_INVALID, "filter matrix missing");
