@@ -18,12 +18,15 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 SRC = ["csrc/kernels_nt1.hip", "csrc/kernels_nt2.hip", "csrc/kernels_nt4.hip",
-       "csrc/kernels_common.hip", "csrc/plan.hip", "csrc/metrics.hip", "csrc/floodmaps.hip", "csrc/series.hip",
+       "csrc/kernels_common.hip", "csrc/plan.hip", "csrc/weights.hip", "csrc/schedule.hip", "csrc/runtime.hip",
+       "csrc/metrics.hip", "csrc/floodmaps.hip", "csrc/series.hip",
        "csrc/train.hip", "csrc/loss.hip", "csrc/ensemble.hip", "csrc/scores.hip", "csrc/raster.hip",
        "csrc/zonal.hip"]
-HDR = ["csrc/engine.h", "csrc/kernels_impl.h", "csrc/tiling.h", "csrc/graph_build.h", "csrc/raster_handle.h",
-       os.path.join(ROOT, "include", "mswegnn.h")]
-HDR += sorted(os.path.join("csrc", "kernels", f) for f in os.listdir(os.path.join(HERE, "csrc", "kernels")) if f.endswith(".h"))
+# every header under csrc/, in sorted order: a header left out would mean a stale library that
+# reports itself current (the staleness check and source_hash() go by this list)
+HDR = [os.path.join(ROOT, "include", "mswegnn.h")]
+for _d in ("csrc", os.path.join("csrc", "kernels")):
+    HDR += sorted(os.path.join(_d, f) for f in os.listdir(os.path.join(HERE, _d)) if f.endswith(".h"))
 ARCH = os.environ.get("MSW_OFFLOAD_ARCH", "gfx950")
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-result",
          "-I", os.path.join(ROOT, "include")]

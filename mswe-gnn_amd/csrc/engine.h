@@ -1,4 +1,4 @@
-// Internal interface between the host plan (plan.hip) and the gfx950 kernels
+// Internal interface between the host side (plan.h and its units) and the gfx950 kernels
 // (kernels_impl.h, instantiated per F in kernels_nt*.hip).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -30,7 +30,7 @@ struct MlpDev {
 
 // Weight region of one launch: blob floats [off, off+len) (len % 4 == 0) copied into LDS
 // by every workgroup before use; the operand offsets in that launch's arguments are then
-// LDS offsets (plan.hip: relocate).  F = 64 launches read the blob in place (len = 0).
+// LDS offsets (weights.hip relocate).  F = 64 launches read the blob in place (len = 0).
 struct WReg {
   int off, len;
   int split;  // floats needed before the epilogue; [split, len) = epilogue operands (or len)
@@ -281,7 +281,7 @@ struct PoolArgs {
   int coop;                // edge tiles: 2 = two waves per tile (projection split), else one
 };
 
-// Epilogue of a layer's last hop on dense 16-row node tiles (large scales, plan.hip
+// Epilogue of a layer's last hop on dense 16-row node tiles (large scales, schedule.hip
 // sched_proc): the hop runs as a middle hop and stores its result rows (before post_act);
 // this launch applies what follows the hop (node_epilogue) to rows [n0, n0 + ns).  An edge
 // tile holds ~5 destinations of its <= 16 rows on a triangular mesh, so the epilogue's

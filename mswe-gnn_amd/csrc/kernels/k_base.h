@@ -162,7 +162,7 @@ __device__ __forceinline__ int wave_row0() { return (blockIdx.x * kWaves + wave_
 // x > 0 ? x : slope x for every x -- infinities and NaN included -- except the sign of a zero
 // output when x = +0 and slope < 0 (+0 instead of -0), which no consumer can see: every PReLU
 // output feeds an MFMA chain or a sum that starts from +0, or a comparison with 0.  The host
-// checks the slopes per plan (plan.hip all_prelu); other slopes run the run-time switch, whose
+// checks the slopes per plan (weights.hip all_prelu); other slopes run the run-time switch, whose
 // PReLU is ACT = 8 (the reference's form).
 #ifndef MSW_PRELU_MAX
 #define MSW_PRELU_MAX 1  // 0: the reference's form for ACT = 1 too (A/B build variant)

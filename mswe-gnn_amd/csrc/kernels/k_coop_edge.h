@@ -352,7 +352,7 @@ __device__ __forceinline__ void unpool_row(f32x4 (&res)[NT], const UnpoolIn<NT>&
 #pragma unroll
     for (int t = 0; t < NT; ++t) sv[t] = H[t];
   }
-  // (no mask_pad: unpooling is fused at NT = 2 only, plan.hip unpool_fusable -- never padded)
+  // (no mask_pad: unpooling is fused at NT = 2 only, schedule.hip unpool_fusable -- never padded)
   if (d.normalize) normalize_s<NT>(sv);  // gnn.py:424-426
   // put_message with the destination's rows zero (own_zero), then its one-edge sum
   float rs = 0.f, rd = 0.f;

@@ -346,7 +346,7 @@ void k_edge_hop(EdgeHopArgs a) {
         c.W = smem;
         Wm = smem;
         if (split) stage_glds<WV>(smem, a.c.W, a.reg, chunk_ceil(a.reg.split), a.reg_nf);
-      } else if (a.reg.len > 0) {  // F = 64: the MLP region alone (plan.hip relocate)
+      } else if (a.reg.len > 0) {  // F = 64: the MLP region alone (weights.hip relocate)
         stage_glds<WV>(smem, a.c.W, a.reg, 0, a.reg.len);
         __syncthreads();
         Wm = smem;
@@ -407,7 +407,7 @@ void k_edge_hop(EdgeHopArgs a) {
 }
 
 // ---------------------------------------------------------------------------- edge MLP alone
-// F = 64 scales whose edge tiles exceed one round of the fused kernel (plan.hip sched_proc,
+// F = 64 scales whose edge tiles exceed one round of the fused kernel (schedule.hip sched_proc,
 // MSW_SPLIT_EDGE_MLP): the edge MLP of a layer's first hop on its own, s for every edge;
 // hop 1 then runs as a k_hop launch.  Without the hop state (source / own rows, filter,
 // node -> edge slab) the kernel fits two waves per SIMD where the fused kernel runs one, and

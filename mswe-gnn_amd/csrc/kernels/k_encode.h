@@ -214,7 +214,7 @@ __global__ __launch_bounds__(kBlock) void k_encode(EncodeArgs a) {
 }
 
 // ---------------------------------------------------------------------------- forward decode
-// Forward mode with the deferred decoder (plan.hip sched_step): decode_rows -- the last hops'
+// Forward mode with the deferred decoder (schedule.hip sched_step): decode_rows -- the last hops'
 // forward-mode epilogue, operation for operation -- on 16 stored last-layer rows per wave,
 // after the whole schedule instead of inside four latency-bound last hops.  The decoder
 // operands are read from the blob (a few KB, L2-resident): no staging barrier.

@@ -1,5 +1,5 @@
 """Every grid-stride kernel of the large-mesh path, on small meshes, making several loop
-iterations per wave (MSW_GRID_CAP, plan.hip Knobs).
+iterations per wave (MSW_GRID_CAP, plan.h Knobs).
 
 The large-mesh family (grid-stride k_encode, k_edge_hop<.., LOOP>, k_hop<.., LOOP>, k_hop_rows on
 a capped grid, the row-layout k_pool, k_epi<.., LOOP>, the capped k_edge_mlp) is otherwise reached

@@ -4,7 +4,7 @@ RCCL refuses two ranks on one device, so the multi-GPU paths are driven here thr
 communicators:
   * halo exchange: a plan of the undivided mesh whose exchange list holds SELF entries (peer ==
     rank, msw_plan_create_part) runs every exchange point of msw_rollout through the real
-    transport -- pack rows, grouped ncclSend / ncclRecv to self, unpack (plan.hip
+    transport -- pack rows, grouped ncclSend / ncclRecv to self, unpack (runtime.hip
     rccl_exchange).  Identity entries (send row k = receive row k) must leave the rollout bit
     for bit as the plain plan's; shifted entries (receive row k <- send row k+1) must move rows
     exactly as the in-process transport does (msw_group_rollout, device copies, no RCCL);

@@ -1,5 +1,5 @@
 """Randomised engine schedules (fixed seeds, deterministic): every MSW_* switch is documented
-as flipping between bit-identical variants (plan.hip Knobs), and each switch has its own test
+as flipping between bit-identical variants (plan.h Knobs), and each switch has its own test
 that flips it alone.  This draws COMBINATIONS of switches — including the size thresholds
 (MSW_COOP_WAVES, MSW_EPI_SPLIT_TILES) set low or high enough to put the large-mesh kernels on
 small meshes and the small-mesh kernels on larger ones — on random models (MSGNN with 2-4
@@ -23,7 +23,7 @@ from mswegnn.rollout import rollout_test
 
 pytestmark = pytest.mark.gpu
 
-# the non-default values of each engine switch (plan.hip knobs_from_env)
+# the non-default values of each engine switch (plan.h knobs_from_env)
 KNOB_VALUES = {
     "MSW_SPLIT_EDGE_MLP": ["0", "1"],
     "MSW_POOL_FUSE": ["0"],

@@ -61,6 +61,24 @@ def test_abi_struct_layouts_and_version(libso):
     assert isinstance(libso.msw_last_error(), bytes)
 
 
+def test_build_lists_every_source_and_header():
+    """build_engine compiles every csrc/*.hip (SRC) and watches every header under csrc/ and the
+    public header (HDR: the staleness check and source_hash() go by it), in a fixed order."""
+    sys.path.insert(0, PKG)
+    import build_engine
+    csrc = os.path.join(PKG, "csrc")
+    hips = sorted("csrc/" + f for f in os.listdir(csrc) if f.endswith(".hip"))
+    assert hips and sorted(build_engine.SRC) == hips and len(set(build_engine.SRC)) == len(build_engine.SRC)
+    hdrs = sorted(os.path.join(d, f) for d, _, fs in os.walk(csrc) for f in fs if f.endswith(".h"))
+    listed = [os.path.normpath(h if os.path.isabs(h) else os.path.join(PKG, h)) for h in build_engine.HDR]
+    assert os.path.join(csrc, "plan.h") in hdrs and len(hdrs) > 10
+    assert sorted(listed) == sorted(hdrs + [os.path.normpath(HEADER)]), set(listed) ^ set(hdrs)
+    per_dir = {}
+    for h in listed:
+        per_dir.setdefault(os.path.dirname(h), []).append(h)
+    assert all(v == sorted(v) for v in per_dir.values()), "HDR must be in sorted order (a deterministic hash)"
+
+
 def test_abi_rejects_null_arguments_without_gpu(libso):
     """Argument validation happens before any HIP call: null plans / descriptors are
     reported through the error code + msw_last_error, never a crash."""
@@ -515,7 +533,7 @@ int main() {  // stdin: n deg_0 .. deg_{n-1}; stdout: the order
 
 
 def _greedy_tiles(deg):
-    """plan.hip build_tiles: consecutive destinations, <= 16 in-edges and <= 16 per tile."""
+    """graph_build.h build_tiles: consecutive destinations, <= 16 in-edges and <= 16 per tile."""
     n = a = 0
     while a < len(deg):
         b, e = a, 0
