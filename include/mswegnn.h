@@ -677,6 +677,99 @@ int msw_zonal_frames(const msw_zonal* zonal, const float* frames, int64_t frame_
  * MSW_ERR_INVALID: a NULL output, num_faces negative.  Host only. */
 int msw_zonal_launch(int64_t num_faces, int32_t* grid, int32_t* faces_per_wg, int32_t* iters);
 
+/* Mesh graphs: the way INTO the engine from a plain triangulation -- arbitrary points located in
+ * the triangles of one mesh scale, and the dual graph of one scale from its coordinates and vertex
+ * lists alone.  mswegnn/meshgraph.py assembles both into a multiscale graph in the reference's
+ * layout (database/graph_creation.py builds its graphs on the host with meshkernel, networkx and
+ * one matplotlib Path.contains_points call per coarse face, O(N_coarse * N_fine)).  Every index is
+ * decided by the fp64 predicates of "Raster products" or by vertex lists; every float64 output is
+ * a stated sequence of IEEE operations, each rounded on its own (no fma).
+ *
+ * a) Point locator.  Geometry as for msw_raster_create (HOST arrays; face_row NULL: f; -1: the face
+ * takes part and yields -1), the same face records, bucket grid and rounding margin, no pixel grid.
+ *     rows[i] = face_row[f] of the LOWEST face f that contains (xy[i][0], xy[i][1]), else -1,
+ * "contains" being exactly the rule of "Raster products": the edge functions taken from the lower
+ * vertex index, E >= 0 (area2 > 0) or E <= 0 (area2 < 0) on all three edges, a face with area2 == 0
+ * contains nothing.  A point outside the bucket grid (the faces' bounding boxes, each widened by
+ * its margin) gets -1 without touching memory; so does a point with a NaN or an infinite
+ * coordinate.  msw_locator_create is host-synchronous (the build and three uploads, no kernel);
+ * msw_locate_points (xy device float64 [n][2], rows device int32 [n]) is stream-ordered, without
+ * host synchronisation or allocation, and only reads the handle.  n = 0: no-op.
+ * MSW_ERR_INVALID: as msw_raster_create for the geometry; NULL loc, xy or rows; negative n; xy not
+ * 8-byte or rows not 4-byte aligned.  MSW_ERR_UNSUPPORTED: more than 2^26 faces. */
+typedef struct {
+  int64_t buckets;            /* buckets of the host-built grid (buckets_x * buckets_y)             */
+  int64_t list_entries;       /* face indices over all bucket lists                                 */
+  int64_t longest_list;       /* faces in the longest bucket list                                   */
+  int64_t device_bytes;       /* device memory the handle owns                                      */
+  double  host_build_seconds; /* host time of the checks, the face records and the bucket grid      */
+  int32_t buckets_x, buckets_y;
+} msw_locator_stats;
+
+typedef struct msw_locator msw_locator;
+int msw_locator_create(const double* node_xy, int64_t num_nodes, const int32_t* face_nodes,
+                       const int32_t* face_row, int64_t num_faces, int device, msw_locator** out);
+int msw_locator_destroy(msw_locator* loc);
+int msw_locator_get_stats(const msw_locator* loc, msw_locator_stats* stats);
+int msw_locate_points(const msw_locator* loc, const double* xy, int64_t n, int32_t* rows, void* stream);
+/* The launch of the locate kernel for n points (from the code the launcher itself uses): one-wave
+ * workgroups, each taking points_per_wg = 64 consecutive points per round of its loop, at most 4096
+ * workgroups, so that grid * 64 * iters >= n.  n = 0: grid and iters are 0.
+ * MSW_ERR_INVALID: a NULL output, n negative.  Host only. */
+int msw_locate_launch(int64_t n, int32_t* grid, int32_t* points_per_wg, int32_t* iters);
+
+/* b) Dual graph of one scale: graph nodes are faces, two faces are joined when they share an edge.
+ * From node_xy float64 [num_nodes][2] and face_nodes int32 [num_faces][3] (HOST arrays; faces in
+ * either orientation, vertices that no face uses allowed) msw_mesh_dual_create builds and owns, on
+ * the device, with a = face_nodes[f][0], b = [1], c = [2]:
+ *   centroid    float64 [num_faces][2]: ((a.x + b.x) + c.x) / 3.0, y likewise;
+ *   area        float64 [num_faces]: 0.5 * fabs((b.x - a.x) * (c.y - a.y) - (c.x - a.x) * (b.y - a.y));
+ *   adjacent    int32 [num_faces][3]: slot 0 is the edge (a, b), 1 (b, c), 2 (c, a); the other face
+ *               that holds both vertices of the edge, -1 where there is none (a boundary edge);
+ *   edge_index  int64 [2][num_edges]: every dual edge in both directions, sorted by (row, column):
+ *               rows ascend, the columns of a row ascend (PyG to_undirected's coalesced order);
+ *   edge_length float64 [num_edges]: dx = centroid[col].x - centroid[row].x, dy likewise,
+ *               sqrt(dx * dx + dy * dy), the root rounded to nearest like the other operations (the
+ *               kernel corrects the device's sqrt with one exact residual);
+ *   boundary    int32 [num_boundary][2]: the (face, slot) pairs with adjacent == -1, face-major,
+ *               slots ascending; num_edges + num_boundary = 3 * num_faces.
+ * Create is host-synchronous: the host checks each face and builds a vertex -> incident-faces CSR
+ * (faces ascending in every list), a kernel (lane = face) computes centroid, area, adjacent and the
+ * number of neighbours by walking the star of each edge's lower vertex, the host takes the prefix
+ * sum, a second kernel (lane = face) writes edge_index, edge_length and boundary.  No atomics: no
+ * output bit depends on an order of execution.  Both kernels run on `stream`; create waits for it.
+ * MSW_ERR_INVALID with a message "face F: ...": the checks run in this order and the message names
+ * the lowest face that fails the first check that fails --
+ *   faces one at a time: a vertex index outside [0, num_nodes), a repeated vertex, a non-finite
+ *   coordinate, area2 zero or not finite;
+ *   then a non-finite coordinate of a vertex that no face uses (no face is named);
+ *   then, over the whole mesh: an edge shared by more than two faces, two faces that share more than
+ *   one edge.
+ * Also MSW_ERR_INVALID: NULLs, negative counts, device < 0.  MSW_ERR_UNSUPPORTED: more than 2^26
+ * faces.  A refusal leaves nothing allocated.  num_faces = 0: every array is empty (NULL). */
+typedef struct {
+  int64_t num_faces, num_edges, num_boundary;
+  int64_t longest_star;       /* faces round the vertex with the most                               */
+  int64_t device_bytes;       /* device memory the handle owns                                      */
+  double  host_build_seconds; /* host: the checks, the vertex CSR, the prefix sum                   */
+  double  create_seconds;     /* host clock around all of create: host build, copies, both kernels  */
+  double  faces_us, edges_us; /* device time of the two kernels (events around each)                */
+} msw_mesh_dual_stats;
+
+typedef struct msw_mesh_dual msw_mesh_dual;
+int msw_mesh_dual_create(const double* node_xy, int64_t num_nodes, const int32_t* face_nodes,
+                         int64_t num_faces, int device, void* stream, msw_mesh_dual** out);
+int msw_mesh_dual_destroy(msw_mesh_dual* dual);
+/* The handle's device arrays; they live as long as the handle. */
+int msw_mesh_dual_arrays(const msw_mesh_dual* dual, const double** centroid, const double** area,
+                         const int32_t** adjacent, const int64_t** edge_index, const double** edge_length,
+                         int64_t* num_edges, const int32_t** boundary, int64_t* num_boundary);
+int msw_mesh_dual_get_stats(const msw_mesh_dual* dual, msw_mesh_dual_stats* stats);
+/* The launch of both dual-graph kernels over num_faces faces: one-wave workgroups, faces_per_wg =
+ * 64 consecutive faces per round, at most 4096 workgroups, grid * 64 * iters >= num_faces.
+ * num_faces = 0: grid and iters are 0.  MSW_ERR_INVALID: a NULL output, num_faces negative. */
+int msw_mesh_dual_launch(int64_t num_faces, int32_t* grid, int32_t* faces_per_wg, int32_t* iters);
+
 /* ---- Training: autograd through one SWEGNN processor ------------------------
  * Replaces the autograd of SWEGNN.forward (models/gnn.py:387-445) the reference trains through
  * in training_step (training/train.py:125-145).  Stateless: every buffer is device memory the

@@ -270,7 +270,7 @@ int64_t msw_struct_size(const char* name) {
       MSW_SIZE(msw_mlp_grads), MSW_SIZE(msw_flood_maps), MSW_SIZE(msw_zone_series),
       MSW_SIZE(msw_train_loss_desc), MSW_SIZE(msw_ensemble_steps_out), MSW_SIZE(msw_ensemble_maps_out),
       MSW_SIZE(msw_ensemble_scores_out), MSW_SIZE(msw_raster_grid), MSW_SIZE(msw_raster_stats),
-      MSW_SIZE(msw_zonal_stats)};
+      MSW_SIZE(msw_zonal_stats), MSW_SIZE(msw_locator_stats), MSW_SIZE(msw_mesh_dual_stats)};
 #undef MSW_SIZE
   for (const auto& t : tab)
     if (name && !strcmp(name, t.name)) return t.size;

@@ -8,7 +8,8 @@ binding (``_lib``), plans (``engine``), the rollout-path operators and the fused
 on-device metrics (``metrics``), on-device flood maps and chunked rollouts (``floodmaps``), on-device
 zone series (``series``), on-device ensemble products and the
 scores of an ensemble against a truth run (``ensemble``), maps and rollout frames resampled
-onto regular grids (``raster``), the training layers'
+onto regular grids (``raster``), multiscale graphs from plain triangulations and graph rows from
+(x, y) points (``meshgraph``), the training layers'
 autograd (``autograd``), the training loss (``loss``) and the synthetic meshes (``mesh``).
 """
 import os

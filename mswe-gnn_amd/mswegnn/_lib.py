@@ -160,6 +160,19 @@ class MswZonalStats(C.Structure):
                 ("build_us", C.c_double)]
 
 
+class MswLocatorStats(C.Structure):
+    _fields_ = [("buckets", C.c_int64), ("list_entries", C.c_int64), ("longest_list", C.c_int64),
+                ("device_bytes", C.c_int64), ("host_build_seconds", C.c_double),
+                ("buckets_x", C.c_int32), ("buckets_y", C.c_int32)]
+
+
+class MswMeshDualStats(C.Structure):
+    _fields_ = [("num_faces", C.c_int64), ("num_edges", C.c_int64), ("num_boundary", C.c_int64),
+                ("longest_star", C.c_int64), ("device_bytes", C.c_int64),
+                ("host_build_seconds", C.c_double), ("create_seconds", C.c_double),
+                ("faces_us", C.c_double), ("edges_us", C.c_double)]
+
+
 MAX_LOSS_RANGES = 64
 TRAIN_LOSS_RECORD = 12
 LOSS_TYPE = {"RMSE": 0, "MAE": 1}
@@ -240,6 +253,20 @@ SYMBOLS = [
     ("msw_zonal_frames", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
                                    C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_uint32, C.c_void_p]),
     ("msw_zonal_launch", C.c_int, [C.c_int64, c_int32_p, c_int32_p, c_int32_p]),
+    ("msw_locator_create", C.c_int, [C.POINTER(C.c_double), C.c_int64, c_int32_p, c_int32_p, C.c_int64, C.c_int,
+                                     C.POINTER(C.c_void_p)]),
+    ("msw_locator_destroy", C.c_int, [C.c_void_p]),
+    ("msw_locator_get_stats", C.c_int, [C.c_void_p, C.POINTER(MswLocatorStats)]),
+    ("msw_locate_points", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    ("msw_locate_launch", C.c_int, [C.c_int64, c_int32_p, c_int32_p, c_int32_p]),
+    ("msw_mesh_dual_create", C.c_int, [C.POINTER(C.c_double), C.c_int64, c_int32_p, C.c_int64, C.c_int, C.c_void_p,
+                                       C.POINTER(C.c_void_p)]),
+    ("msw_mesh_dual_destroy", C.c_int, [C.c_void_p]),
+    ("msw_mesh_dual_arrays", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                       C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                       c_int64_p, C.POINTER(C.c_void_p), c_int64_p]),
+    ("msw_mesh_dual_get_stats", C.c_int, [C.c_void_p, C.POINTER(MswMeshDualStats)]),
+    ("msw_mesh_dual_launch", C.c_int, [C.c_int64, c_int32_p, c_int32_p, c_int32_p]),
     ("msw_plan_create_part", C.c_int, [C.POINTER(MswGraphDesc), C.POINTER(MswModelDesc), C.c_int,
                                        C.POINTER(MswExchangeDesc), C.c_int32, C.POINTER(C.c_void_p)]),
     ("msw_comm_unique_id", C.c_int, [C.c_char_p]),
@@ -280,7 +307,8 @@ STRUCTS = {"msw_linear": MswLinear, "msw_mlp": MswMlp, "msw_swegnn": MswSwegnn,
            "msw_ensemble_steps_out": MswEnsembleStepsOut, "msw_ensemble_maps_out": MswEnsembleMapsOut,
            "msw_ensemble_scores_out": MswEnsembleScoresOut,
            "msw_raster_grid": MswRasterGrid, "msw_raster_stats": MswRasterStats,
-           "msw_zonal_stats": MswZonalStats}
+           "msw_zonal_stats": MswZonalStats, "msw_locator_stats": MswLocatorStats,
+           "msw_mesh_dual_stats": MswMeshDualStats}
 
 _lib = None
 
