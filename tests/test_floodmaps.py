@@ -2,6 +2,9 @@
 reference's own functions (tests/golden/fx_floodmaps.npz, tools/gen_golden_floodmaps.py, and the
 reference tree itself where present), ``rollout_chunks`` on the torch path against the whole
 rollout bit for bit, and the host side of the C ABI (error returns, no-ops, the launch query).
+Then the kernel's test cases themselves (tests/floodmaps_cases.py): a census of the staging
+geometries the launch query reports against the windows the GPU sweep runs, the part-by-part
+restatement against ``_maps_torch``, and every wrong variant of it caught in every class.
 """
 import ctypes as C
 import os
@@ -11,6 +14,7 @@ import numpy as np
 import pytest
 import torch
 
+import floodmaps_cases as fc
 from conftest import ROOT, build_msgnn, golden, weights
 from mswegnn import _lib
 from mswegnn import floodmaps as fmod
@@ -215,3 +219,56 @@ def test_abi_launch_edge_cases(lib):
     assert (g.value, it.value) == (0, 0)
     assert lib.msw_flood_maps_launch(-1, 8, C.byref(g), C.byref(r), C.byref(it)) == -1
     assert lib.msw_flood_maps_launch(8, 8, None, C.byref(r), C.byref(it)) == -1
+
+
+# ------------------------------------------------------------------ the kernel's test cases
+def test_census_of_staging_geometries(lib):
+    """Every rows-per-round class of the launch query runs with both loaders, and both sides of
+    every class edge are windows of the sweep: retuning the kernel's LDS budget without extending
+    tests/floodmaps_cases.py fails here."""
+    r = {tc: fc.rows_per_wg(tc) for tc in range(1, fc.SLAB + 1)}
+    classes = sorted(set(r.values()))
+    edges = [tc for tc in range(2, fc.SLAB + 1) if r[tc] != r[tc - 1]]      # the first t_count of a class
+    assert len(classes) >= 2 and len(edges) == len(classes) - 1
+    assert fc.rows_per_wg(fc.SLAB + 1) == r[fc.SLAB] and fc.rows_per_wg(5 * fc.SLAB) == r[fc.SLAB]
+    ran = {(tc, vec) for c in fc.CASES for tc, _, vec in c.launches()}
+    steps = {tc for tc, _ in ran}
+    for e in edges:
+        assert e - 1 in steps and e in steps, f"no window on both sides of the class edge {e - 1} | {e}"
+    for R in classes:
+        for vec in (False, True):
+            assert any(r[tc] == R and v == vec for tc, v in ran), f"rows_per_wg {R} never runs with vec={vec}"
+    # the loaders are what the cases say: the 16-byte one needs the whole window of an even T
+    assert all(c.vec == (c.T in fc.VEC_T and c.t_begin == 0 and c.t_count == c.T and not c.shift) for c in fc.CASES)
+    # the carry-over cases are one class each of 4, 2 and 1 rows per round
+    assert {fc.rows_per_wg(min(T, fc.SLAB)) for T, _ in fc.CARRY} == {4, 2, 1}
+    assert all(sum(pieces) == T for T, pieces in fc.CARRY)
+
+
+def test_planted_rows_sit_where_the_geometry_says():
+    assert fc.part_starts(132) == list(range(0, 132, 9)) and len(fc.part_starts(132)) == 15   # the 16th part is empty
+    assert fc.part_starts(200) == list(range(0, 200, 13))
+    assert fc.part_starts(1025) == list(range(0, 1024, 16)) + [1024]
+    r = fc.planted_rollout(fc.PERIOD, 132, 0, 132, seed=1)
+    h = r[:, 0, :]
+    assert int(h[8 + 7].argmax()) == 131 and float(h[8 + 7].max()) == 3.0
+    assert h[8 + 2, 125] == h[8 + 2, 126] == 3.0                 # across the last non-empty boundary
+    assert bool((h[8 + 6, 63:72] == 0).all()) and float(h[8 + 6, 62]) > 0 and float(h[8 + 6, 72]) > 0
+    r = fc.planted_rollout(fc.PERIOD, 2049, 0, 2049, seed=1)
+    assert r[8 + 8, 0, 1023] == r[8 + 8, 0, 1024] == 3.0 and r[8 + 10, 0, 2047] == r[8 + 10, 0, 2048] == 3.0
+    assert bool((r[8 + 9, 0, :1024] == 0).all()) and float(r[8 + 9, 0, 1024]) > 0.05
+
+
+@pytest.mark.parametrize("case", fc.CASES, ids=[c.id for c in fc.CASES])
+def test_restatement_and_sensitivity(case):
+    """On the planted rows of the case: the part-by-part restatement equals ``_maps_torch``, and
+    every wrong variant of it changes a map that the GPU sweep asserts."""
+    host = fc.case_rollout(case, fc.PERIOD)
+    rows = host[8:, :, case.t_begin:case.t_begin + case.t_count]
+    want = fc.yardstick(rows)
+    starts = fc.part_starts(case.t_count)
+    got = fc.maps_by_parts(rows, fc.THR4, fc.EPS, fc.T_OFFSET, starts)
+    assert fc.changed_maps(got, want) == []
+    assert fc.changed_maps(fc.maps_by_parts(rows, fc.THR4, fc.EPS, fc.T_OFFSET, [0]), want) == []
+    for v in fc.VARIANTS:
+        assert fc.changed_maps(fc.maps_by_parts(rows, fc.THR4, fc.EPS, fc.T_OFFSET, starts, v), want), v

@@ -20,13 +20,21 @@ checked twice:
     nearest adds at most half an ulp each; a maximum over time moves no further than its terms.
 Then: the engine's rollout run in chunks against the whole rollout, bit for bit, and reduced to
 maps chunk by chunk.
+
+The staging geometry (rows per round x time parts, tests/floodmaps_cases.py) changes at 33, 66, 132,
+264 and 528 steps, and each class runs with the 16-byte and the scalar loader:
+``test_every_geometry_equals_maps_torch`` steps over every edge with both, with rows planted at
+the part and slab boundaries of the launch that reduces them, and ``test_carry_over_across_parts_and_slabs``
+cuts the long classes inside a part, on a part boundary and at the 1024-step slab.
 """
 import ctypes as C
 
 import pytest
 import torch
 
+import floodmaps_cases as fc
 from conftest import build_msgnn, golden, weights
+from floodmaps_cases import EPS, THR4, f32, make_rollout
 from mswegnn import _lib
 from mswegnn.batch import collate
 from mswegnn.floodmaps import MAP_NAMES, FloodMaps, _maps_torch, flood_maps, rollout_chunks, rollout_flood_maps
@@ -37,8 +45,6 @@ from mswegnn.rollout import adapt_batch_training
 pytestmark = pytest.mark.gpu
 
 FX = golden("fx_floodmaps")
-THR4 = (0.05, 0.3, 0.0, 1.0)
-EPS = 0.01
 PAD = 37          # canary words on each side of every output array
 CANARY_F, CANARY_I = -12345.5, -123456789
 POISON = 7.0e8    # rows outside the requested range: reading one would change a maximum
@@ -77,39 +83,6 @@ def check_map(k, got, want, label=""):
         assert d <= FROUDE_ULP, f"{label}: froude_max {d} ulp from the torch composition"
     else:
         assert torch.equal(got, want[k]), f"{label}: {k}"
-
-
-def f32(v):
-    return float(torch.tensor(v, dtype=torch.float32))
-
-
-def make_rollout(n, T, seed):
-    """[n, 2, T] seeded values on a 2^-12 grid (no denormals anywhere, also not in q / h), with
-    planted rows, cycling over the row index: never wet; always wet; wet - dry - wet; the maximum
-    of h and of |q| tied at two steps (q with opposite signs); h exactly at the thresholds, at
-    vel_eps and at 0; 0 < h < vel_eps throughout; two plain random rows."""
-    gen = torch.Generator().manual_seed(seed)
-    h = torch.round(torch.rand(n, T, generator=gen) * 1.5 * 4096) / 4096
-    h = torch.where(torch.rand(n, T, generator=gen) < 0.45, torch.zeros(()), h)
-    q = torch.round((torch.rand(n, T, generator=gen) * 2 - 1) * 4096) / 4096   # negative discharges too
-    q = torch.where(torch.rand(n, T, generator=gen) < 0.2, torch.zeros(()), q)
-    kind = torch.arange(n) % 8
-    t = torch.arange(T)
-    h[kind == 0] = 0.0
-    q[kind == 0] = 0.0
-    h[kind == 1] += 0.5
-    third = max(T // 3, 1)
-    mid = (t >= third) & (t < T - third)
-    h[kind == 2] = torch.where(mid, torch.zeros(()), h[kind == 2] + 0.25)
-    t1, t2 = (T // 4) % T, (T - 1 - T // 5) % T
-    for tt, sign in ((t1, -1.0), (t2, 1.0)):
-        h[kind == 3, tt] = 3.0
-        q[kind == 3, tt] = sign * 2.0
-    for i, v in enumerate((f32(0.05), f32(0.3), f32(EPS), 0.0, 1.0)):
-        h[kind == 4, i % T] = v
-    h[kind == 5] = 0.005
-    q[kind == 5] = 0.75
-    return torch.stack((h, q), 1).contiguous()
 
 
 class Buffers:
@@ -194,6 +167,29 @@ def test_shape_sweep_equals_maps_torch(cuda, T, t_begin, t_count):
                 assert_maps(bufs, want, n_thr, f"nrows={nrows} row0={row0} n_thr={n_thr}")
 
 
+@pytest.mark.parametrize("case", fc.CASES, ids=[c.id for c in fc.CASES])
+def test_every_geometry_equals_maps_torch(cuda, case):
+    sizes = case.row_counts()
+    total = max(sizes) + 5 + 3
+    T, tb, tc = case.T, case.t_begin, case.t_count
+    host = fc.case_rollout(case, total)
+    whole = expected(host[:, :, tb:tb + tc], THR4, fc.T_OFFSET)     # rows reduce independently: computed once
+    store = torch.zeros(total * 2 * T + 8, device=cuda)
+    dev = store[case.shift:case.shift + total * 2 * T].view(total, 2, T)
+    assert dev.data_ptr() % 16 == (4 * case.shift) % 16
+    for nrows in sizes:
+        for row0 in (0, 5):
+            inside = host.clone()
+            inside[:row0] = POISON
+            inside[row0 + nrows:] = POISON
+            dev.copy_(inside)
+            want = {k: v[..., row0:row0 + nrows] for k, v in whole.items()}
+            for n_thr in (0, 4):
+                bufs = Buffers(nrows, n_thr, cuda)
+                update(dev, bufs, tb, tc, fc.T_OFFSET, row0, nrows, THR4[:n_thr])
+                assert_maps(bufs, want, n_thr, f"{case.id} nrows={nrows} row0={row0} n_thr={n_thr}")
+
+
 def test_misaligned_base_takes_the_scalar_loader(cuda):
     T, n = 48, 257
     host = make_rollout(n, T, seed=3)
@@ -255,6 +251,29 @@ def test_carry_over_equals_one_shot(cuda, split, how):
             update(dev[:, :, t0:t0 + c].contiguous(), bufs, 0, c, t0, 4, n, thr, first=int(t0 == 0))
         t0 += c
     assert_maps(bufs, want, 3, f"{how} {split}")
+
+
+@pytest.mark.parametrize("T, split", fc.CARRY, ids=[f"T{T}-" + "+".join(map(str, p)) for T, p in fc.CARRY])
+@pytest.mark.parametrize("how", ["windows", "pieces"])
+def test_carry_over_across_parts_and_slabs(cuda, T, split, how):
+    n, thr = fc.PERIOD + 8, THR4[:3]
+    host = fc.planted_rollout(n + 9, T, 0, T, seed=T)
+    dev = host.to(cuda)
+    want = expected(host[4:4 + n], thr)
+    one = Buffers(n, 3, cuda)
+    update(dev, one, 0, T, 0, 4, n, thr)
+    assert_maps(one, want, 3, "one shot")
+    bufs = Buffers(n, 3, cuda)
+    t0 = 0
+    for c in split:
+        if how == "windows":
+            update(dev, bufs, t0, c, t0, 4, n, thr, first=int(t0 == 0))
+        else:
+            update(dev[:, :, t0:t0 + c].contiguous(), bufs, 0, c, t0, 4, n, thr, first=int(t0 == 0))
+        t0 += c
+    assert_maps(bufs, want, 3, f"{how} {split}")
+    for k, v in bufs.view.items():      # and bit for bit the one-shot result, froude_max included
+        assert torch.equal(v, one.view[k]), k
 
 
 @pytest.mark.parametrize("subset", [("wet_steps",), ("h_max", "t_h_max"),

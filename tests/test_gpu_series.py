@@ -10,6 +10,16 @@ volume inside its mass-conservation metric.
     module finishes (pytest -s).
   * however a rollout is cut into windows or pieces, and from call to call: ``torch.equal``.
 Every output sits between canary words, and columns outside a call's window must keep theirs.
+
+On the grid data of ``make_pred`` / ``make_area`` most sums are exact in fp64 in any order, so the
+bound above says little about the order of additions that include/mswegnn.h promises (chunks of
+256 list entries summed in list order from 0, then the chunk sums in chunk order).  The tests named
+``*_wide`` and the slab tests run on full-mantissa data (tests/series_cases.py; a CPU test checks
+that other orders of the same terms differ there in a quarter of the steps or more) and compare
+``volume`` and ``wet_area`` with ``torch.equal`` against ``series_exact``, the documented order
+restated in numpy.  The bound check stays beside it, and its reported worst ratio is now non-zero:
+``_series_torch`` adds in another order.  The slab tests make ``msw_zone_series_update`` cut a window
+into launches of S steps: 1024 by default, 128 and 64 for zone sets of 4096 and 4097 partial chunks.
 """
 import ctypes as C
 
@@ -17,6 +27,7 @@ import numpy as np
 import pytest
 import torch
 
+import series_cases as sc
 from conftest import build_msgnn, golden, manifest, weights
 from mswegnn import _lib
 from mswegnn.batch import collate
@@ -25,11 +36,11 @@ from mswegnn.mesh import make_multiscale_mesh, mesh_config, wet_state
 from mswegnn.metrics import finest_ranges
 from mswegnn.rollout import adapt_batch_training
 from mswegnn.series import SERIES_NAMES, ZoneSeries, Zones, _series_torch, rollout_products, zone_series
+from series_cases import THR4, make_area, make_area_wide, make_pred, make_pred_wide, sweep_zones
 
 pytestmark = pytest.mark.gpu
 
 FX = golden("fx_floodmaps")
-THR4 = (0.05, 0.3, 0.0, 1.0)
 PAD = 37          # canary words on each side of every output array
 CANARY_F, CANARY_I = -12345.5, -123456789
 WORST = {"volume": 0.0, "wet_area": 0.0}   # largest |got - want| / bound seen
@@ -39,26 +50,6 @@ WORST = {"volume": 0.0, "wet_area": 0.0}   # largest |got - want| / bound seen
 def report_worst_ratio():
     yield
     print(f"\nzone series: largest error / bound  volume {WORST['volume']:.3g}  wet_area {WORST['wet_area']:.3g}")
-
-
-def f32(v):
-    return float(torch.tensor(v, dtype=torch.float32))
-
-
-def make_pred(n, T, seed):
-    """[n, 2, T] seeded values on a 2^-12 grid, 45 % of the depths exactly 0, every fifth row
-    cycling through depths exactly at the thresholds; discharges of both signs."""
-    gen = torch.Generator().manual_seed(seed)
-    h = torch.round(torch.rand(n, T, generator=gen) * 1.5 * 4096) / 4096
-    h = torch.where(torch.rand(n, T, generator=gen) < 0.45, torch.zeros(()), h)
-    q = torch.round((torch.rand(n, T, generator=gen) * 2 - 1) * 4096) / 4096
-    at = torch.tensor([f32(0.05), f32(0.3), 0.0, 1.0])
-    h[1::5] = at[(torch.arange(T)[None, :] + torch.arange(h[1::5].shape[0])[:, None]) % 4]
-    return torch.stack((h, q), 1).contiguous()
-
-
-def make_area(n, seed):
-    return torch.rand(n, generator=torch.Generator().manual_seed(seed)) * 90 + 10
 
 
 def expected(pred, zones, area, thr):
@@ -127,14 +118,24 @@ def update(zones, pred, bufs, t_begin, t_count, area, thr, T_out, t_out0, stream
                                                  th, len(thr), T_out, t_out0, C.byref(o), st))
 
 
-def run_case(zones, host, dev, area_host, thr, t_begin, t_count, pad_cols=0, col0=0, label=""):
-    """One raw ABI call into canary buffers, checked against the CPU yardstick."""
+def check_exact(got, ref, label=""):
+    """got: {name: tensor} on any device; ref: ``series_ref`` of the same columns.  Everything
+    bit for bit, the sums included."""
+    for k, v in got.items():
+        assert v.dtype == ref[k].dtype and torch.equal(v.cpu(), ref[k]), f"{label}: {k} differs from the documented order"
+
+
+def run_case(zones, host, dev, area_host, thr, t_begin, t_count, pad_cols=0, col0=0, label="", exact=False):
+    """One raw ABI call into canary buffers, checked against the CPU yardstick (``exact``: and
+    bit for bit against the order-exact restatement)."""
     area_dev = None if area_host is None else area_host.to(dev.device)
     bufs = Buffers(zones.num_zones, len(thr), t_count + pad_cols, dev.device)
     update(zones, dev, bufs, t_begin, t_count, area_dev, thr, t_count + pad_cols, col0)
     bufs.check_canaries(col0, t_count)
     want = expected(host[:, :, t_begin:t_begin + t_count], zones, area_host, thr)
     check_series(bufs.window(col0, t_count), want, zones, label)
+    if exact:
+        check_exact(bufs.window(col0, t_count), sc.series_ref(host[:, :, t_begin:t_begin + t_count], zones, area_host, thr), label)
     if not thr:
         assert not set(bufs.view) & {"wet_area", "wet_cells"}
 
@@ -200,78 +201,183 @@ def test_gauge_identity(cuda):
 
 
 # ------------------------------------------------------------------ 3. shape sweep
-SIZES = (1, 15, 0, 16, 17, 33, 500, 255, 256, 257, 0)   # around a round (16) and a chunk (256); the last is empty
-
-
-def sweep_zones(n, seed):
-    """Zones of SIZES entries drawn with replacement from about 70 % of the rows: unsorted,
-    duplicated, overlapping.  -> (zones, mask of the rows that no zone lists)."""
-    gen = torch.Generator().manual_seed(seed)
-    allowed = torch.nonzero(torch.rand(n, generator=gen) < 0.7).flatten()
-    if allowed.numel() == 0:
-        allowed = torch.zeros(1, dtype=torch.int64)
-    lists = [allowed[torch.randint(0, allowed.numel(), (s,), generator=gen)] for s in SIZES]
-    unlisted = torch.ones(n, dtype=torch.bool)
-    unlisted[torch.cat(lists)] = False
-    return Zones.from_lists(lists, n), unlisted
-
-
-@pytest.mark.parametrize("T", [1, 3, 47, 48, 65, 130, 132])
-def test_shape_sweep(cuda, T):
-    """T = 48 and 132 take the 16-byte loader from an aligned base (132: two full tiles and one of
-    4 steps), every other T and every shifted base the scalar one."""
+def _shape_sweep(cuda, T, wide):
     for n in (1, 17, 64, 65, 1000):
         zones, unlisted = sweep_zones(n, seed=n + T)
-        host = make_pred(n, T, seed=T)
+        host = make_pred_wide(n, T, seed=T) if wide else make_pred(n, T, seed=T)
         host[unlisted] = float("nan")
-        area = make_area(n, 8)
+        area = make_area_wide(n, 8) if wide else make_area(n, 8)
         area[unlisted] = float("nan")
         store = torch.zeros(n * 2 * T + 8, device=cuda)
         for shift, a, thr in ((0, area, THR4[:2]), (1, None, THR4), (2, area, ()), (4, None, THR4[:1])):
             dev = store[shift:shift + n * 2 * T].view(n, 2, T)     # 4 floats = 16 bytes: aligned again
             dev.copy_(host)
             assert dev.data_ptr() % 16 == (4 * shift) % 16
-            run_case(zones, host, dev, a, thr, 0, T, label=f"n={n} T={T} shift={shift}")
+            run_case(zones, host, dev, a, thr, 0, T, label=f"n={n} T={T} shift={shift}", exact=wide)
         # windows: t_begin > 0 (a multiple of 4, and odd), columns t_out0 > 0 of a wider output
         dev = host.to(cuda)
         for t_begin, t_count in ((T // 4 // 4 * 4, T - T // 4 // 4 * 4 - T // 8), (min(3, T - 1), max((T - 3) // 2, 1))):
             run_case(zones, host, dev, area, THR4[:2], t_begin, t_count, pad_cols=9, col0=5,
-                     label=f"n={n} T={T} window=({t_begin}, {t_count})")
+                     label=f"n={n} T={T} window=({t_begin}, {t_count})", exact=wide)
         zones.close()
 
 
+@pytest.mark.parametrize("T", [1, 3, 47, 48, 65, 130, 132])
+def test_shape_sweep(cuda, T):
+    """T = 48 and 132 take the 16-byte loader from an aligned base (132: two full tiles and one of
+    4 steps), every other T and every shifted base the scalar one."""
+    _shape_sweep(cuda, T, wide=False)
+
+
+@pytest.mark.parametrize("T", [1, 3, 47, 48, 65, 130, 132])
+def test_shape_sweep_wide(cuda, T):
+    """The same sweep on full-mantissa data, the sums compared bit for bit with the documented order."""
+    _shape_sweep(cuda, T, wide=True)
+
+
 # ------------------------------------------------------------------ 4. windows, pieces, repeats
-def test_windowing_invariance(cuda):
+def same_result(a, b):
+    for k in ("volume", "h_max", "q_max"):
+        assert torch.equal(a[k], b[k]), k
+    for k in ("wet_area", "wet_cells"):
+        for t in a[k]:
+            assert torch.equal(a[k][t], b[k][t]), (k, t)
+
+
+def result_window(res, thr):
+    """A ``ZoneSeries.result`` as {name: tensor}, the threshold series stacked."""
+    out = {k: res[k] for k in ("volume", "h_max", "q_max")}
+    for k in ("wet_area", "wet_cells"):
+        out[k] = torch.stack([res[k][float(t)] for t in thr])
+    return out
+
+
+def fed_in_pieces(zones, dev, split, how, kw):
+    zs = ZoneSeries(zones, dev.shape[2], device=dev.device, **kw)
+    t0 = 0
+    for c in split:
+        if how == "windows":
+            zs.update(dev, t0, c)
+        else:   # a rollout piece of its own, as rollout_chunks yields them
+            zs.update(dev[:, :, t0:t0 + c].contiguous())
+        t0 += c
+    assert t0 == dev.shape[2]
+    return zs.result()
+
+
+def _windowing_invariance(cuda, wide):
     n, T = 1000, 48
-    host = make_pred(n, T, seed=4)
+    host = make_pred_wide(n, T, seed=4) if wide else make_pred(n, T, seed=4)
     dev = host.to(cuda)
-    area = make_area(n, 9)
-    zones = sweep_zones(n, seed=77)[0] + Zones.from_lists([torch.randperm(n, generator=torch.Generator().manual_seed(1))], n)
+    area = make_area_wide(n, 9) if wide else make_area(n, 9)
+    zones = sweep_zones(n, seed=77)[0] + sc.permutation_zone(n)
     kw = dict(area=area.to(cuda), thresholds=THR4[:3])
     whole = zone_series(dev, zones, **kw)
     host_clean = host.clone()
     check_series({k: whole[k] for k in ("volume", "h_max", "q_max")}, expected(host_clean, zones, area, THR4[:3]), zones)
+    if wide:
+        check_exact(result_window(whole, THR4[:3]), sc.series_ref(host, zones, area, THR4[:3]), "whole")
     again = zone_series(dev, zones, **kw)
-
-    def same(a, b):
-        for k in ("volume", "h_max", "q_max"):
-            assert torch.equal(a[k], b[k]), k
-        for k in ("wet_area", "wet_cells"):
-            for t in a[k]:
-                assert torch.equal(a[k][t], b[k][t]), (k, t)
-    same(again, whole)
+    same_result(again, whole)
     for split in ((1,) * 48, (7, 16, 25), (16, 16, 16), (4, 44)):
         for how in ("windows", "pieces"):
-            zs = ZoneSeries(zones, T, device=cuda, **kw)
-            t0 = 0
-            for c in split:
-                if how == "windows":
-                    zs.update(dev, t0, c)
-                else:   # a rollout piece of its own, as rollout_chunks yields them
-                    zs.update(dev[:, :, t0:t0 + c].contiguous())
-                t0 += c
-            same(zs.result(), whole)
+            same_result(fed_in_pieces(zones, dev, split, how, kw), whole)
     zones.close()
+
+
+def test_windowing_invariance(cuda):
+    _windowing_invariance(cuda, wide=False)
+
+
+def test_windowing_invariance_wide(cuda):
+    """On full-mantissa data, where another order of additions would show: the whole result bit
+    for bit the documented order, and every cut bit for bit the whole."""
+    _windowing_invariance(cuda, wide=True)
+
+
+def test_wet_area_order_with_wide_areas(cuda):
+    """Areas over 1 .. 1e4 add exactly in any order in zones of a few hundred entries; over
+    1 .. 1e11 they round, and ``wet_area`` must follow the documented order as the volume does."""
+    n = sc.N_SLAB
+    zones = sc.default_slab_zones()
+    area = make_area_wide(n, 6, **sc.AREA_SPAN)
+    for T in (48, 47):       # the 16-byte and the scalar loader
+        host = make_pred_wide(n, T, seed=5)
+        run_case(zones, host, host.to(cuda), area, THR4, 0, T, pad_cols=9, col0=5, label=f"wide areas T={T}", exact=True)
+    zones.close()
+
+
+# ------------------------------------------------------------------ 4b. windows longer than one launch
+@pytest.fixture(scope="module")
+def slab_data():
+    """The three multi-launch zone sets with their rollout (CPU), areas and the order-exact series
+    of all its steps, computed once: a step's series depend on no other step, so a shorter T or a
+    window is a slice of the columns."""
+    out = {}
+    for name, (make, S, Ts) in sc.SLAB_SETS.items():
+        zones = make()
+        assert sc.steps_per_launch(zones) == S
+        host = sc.make_pred_wide(sc.N_SLAB, 1032 if name == "default" else 260, seed=5 if name == "default" else 7)
+        host = host[:, :, :max(Ts)].contiguous()
+        area = sc.make_area_wide(sc.N_SLAB, 6)
+        thr = THR4 if name == "default" else THR4[:2]
+        out[name] = dict(zones=zones, S=S, host=host, area=area, thr=thr, ref=sc.series_ref(host, zones, area, thr))
+    yield out
+    for d in out.values():
+        d["zones"].close()
+
+
+def run_slab_case(cuda, d, T, t_begin, t_count, label):
+    """Window [t_begin, t_begin + t_count) of the first T steps as a rollout of its own, into
+    columns 5.. of a wider canary-filled output, bit for bit against the shared reference."""
+    zones, thr = d["zones"], d["thr"]
+    dev = d["host"][:, :, :T].contiguous().to(cuda)
+    assert dev.data_ptr() % 16 == 0 and t_count > d["S"]                     # two launches or more
+    bufs = Buffers(zones.num_zones, len(thr), t_count + 9, cuda)
+    update(zones, dev, bufs, t_begin, t_count, d["area"].to(cuda), thr, t_count + 9, 5)
+    bufs.check_canaries(5, t_count)
+    check_exact(bufs.window(5, t_count), {k: v[..., t_begin:t_begin + t_count] for k, v in d["ref"].items()}, label)
+
+
+@pytest.mark.parametrize("T, t_begin, t_count", [(1028, 0, 1028), (1027, 0, 1027), (1032, 4, 1025)])
+def test_default_slab(cuda, slab_data, T, t_begin, t_count):
+    """S = 1024: 1024 + 4 with the 16-byte loader, 1024 + 3 with the scalar one, and a window
+    1024 + 1 from step 4 (16-byte loader)."""
+    d = slab_data["default"]
+    run_slab_case(cuda, d, T, t_begin, t_count, f"T={T}")
+    if T == 1028:   # beside it, the derived bound against _series_torch (the small zones make it cheap here)
+        run_case(d["zones"], d["host"][:, :, :T].contiguous(), d["host"][:, :, :T].contiguous().to(cuda), d["area"], d["thr"],
+                 0, T, pad_cols=9, col0=5, label="default slab")
+
+
+@pytest.mark.parametrize("T", [132, 131, 260])
+def test_shrunk_slab(cuda, slab_data, T):
+    """S = 128 (4096 partial chunks): 128 + 4 with the 16-byte loader, 128 + 3 with the scalar
+    one, and three launches."""
+    run_slab_case(cuda, slab_data["shrunk"], T, 0, T, f"T={T}")
+
+
+def test_floor_slab(cuda, slab_data):
+    """S = 64, the floor (4097 partial chunks): 64 + 4."""
+    run_slab_case(cuda, slab_data["floor"], 68, 0, 68, "T=68")
+
+
+@pytest.mark.parametrize("name", list(sc.SLAB_SETS))
+def test_chunked_equals_whole_across_slabs(cuda, slab_data, name):
+    """``ZoneSeries.update`` fed in windows and in pieces cut at S - 1, S and S + 1 (so that a
+    piece ends before, at and after the boundary between two launches of the whole, and the longer
+    piece is itself cut into launches): bit for bit the whole, which is the documented order."""
+    d = slab_data[name]
+    S, thr = d["S"], d["thr"]
+    dev = d["host"].to(cuda)
+    T = dev.shape[2]
+    kw = dict(area=d["area"].to(cuda), thresholds=thr)
+    whole = zone_series(dev, d["zones"], **kw)
+    check_exact(result_window(whole, thr), d["ref"], name)
+    for cut in (S - 1, S, S + 1):
+        for split in ((cut, T - cut), (T - cut, cut)):
+            for how in ("windows", "pieces"):
+                same_result(fed_in_pieces(d["zones"], dev, split, how, kw), whole)
 
 
 # ------------------------------------------------------------------ 5. the unit loop

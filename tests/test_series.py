@@ -2,13 +2,17 @@
 values, the ``Zones`` constructors, chunked against whole on the torch path, ``rollout_products``
 against the two separate passes, and the host side of the C ABI (error returns, no-ops, the launch
 query: all of them return before any HIP call; a host-only zone set, device -1, stands in for a
-device one).
+device one).  Then the kernel's test cases themselves (tests/series_cases.py): the order-exact
+restatement against ``_series_torch``, the condition on the data that makes the order of additions
+visible, and a census of the steps per launch of the multi-launch zone sets.
 """
 import ctypes as C
 
+import numpy as np
 import pytest
 import torch
 
+import series_cases as sc
 from conftest import build_msgnn, weights
 from mswegnn import _lib
 from mswegnn.floodmaps import FloodMaps, rollout_flood_maps
@@ -304,3 +308,139 @@ def test_abi_launch_is_consistent(gauges, t_count):
 
 def test_struct_size(lib):
     assert lib.msw_struct_size(b"msw_zone_series") == C.sizeof(_lib.MswZoneSeries) == 40
+
+
+# ------------------------------------------------------------------ the kernel's test cases
+def test_series_ref_equals_series_torch():
+    """``series_ref`` against the yardstick of the other tests: bit for bit on data whose sums are
+    exact in any order (depths on a 2^-12 grid, areas on a 2^-4 grid: every term a multiple of
+    2^-16 below 2^18), and on the wide data the order-free series bit for bit, the sums within
+    2 m 2^-53 sum|terms|."""
+    n, T = 300, 37
+    zones = sc.default_slab_zones() + Zones.gauges([5, 5, 299], n)
+    zone, rows = zones.lists("cpu")
+    wide, area = sc.make_pred_wide(n, T, seed=2), sc.make_area_wide(n, seed=3)
+    grid = torch.round(wide * 4096) / 4096
+    area_grid = torch.round(area * 16) / 16
+    for a in (area_grid, None):
+        want = _series_torch(grid, zone, rows, zones.num_zones, a, sc.THR4)
+        got = sc.series_ref(grid, zones, a, sc.THR4)
+        assert set(got) == set(SERIES_NAMES)
+        for k in SERIES_NAMES:
+            assert got[k].dtype == want[k].dtype and torch.equal(got[k], want[k]), k
+    want = _series_torch(wide, zone, rows, zones.num_zones, area, sc.THR4)
+    got = sc.series_ref(wide, zones, area, sc.THR4)
+    for k in ("wet_cells", "h_max", "q_max"):
+        assert torch.equal(got[k], want[k]), k
+    m = zones.sizes.double()[:, None]
+    for k in ("volume", "wet_area"):     # non-negative terms: sum|terms| is the sum itself
+        assert bool(((got[k] - want[k]).abs() <= 2 * m * 2.0 ** -53 * want[k]).all()), k
+    assert not torch.equal(got["volume"], want["volume"])      # and the order does show
+
+
+def test_series_exact_by_hand():
+    """The documented order restated entry by entry in plain Python floats, on a zone of three
+    chunks (600 entries) and one of one entry."""
+    n, T = 40, 3
+    pred, area = sc.make_pred_wide(n, T, seed=4), sc.make_area_wide(n, seed=5)
+    rows = torch.randint(0, n, (601,), generator=torch.Generator().manual_seed(6))
+    zones = Zones.from_lists([rows[:600], rows[600:]], n)
+    got = sc.series_exact(pred, zones.ptr, zones.rows, area, (0.05,))
+    for t in range(T):
+        sums, wet = [], []
+        for c0 in range(0, 600, 256):
+            v = w = 0.0
+            for r in rows[c0:min(c0 + 256, 600)].tolist():
+                v += float(area[r]) * float(pred[r, 0, t])
+                w += float(area[r]) if float(pred[r, 0, t]) > sc.f32(0.05) else 0.0
+            sums.append(v)
+            wet.append(w)
+        assert got["volume"][0, t] == ((0.0 + sums[0]) + sums[1]) + sums[2]
+        assert got["wet_area"][0, 0, t] == ((0.0 + wet[0]) + wet[1]) + wet[2]
+        r = int(rows[600])
+        assert got["volume"][1, t] == float(area[r]) * float(pred[r, 0, t])
+
+
+def _order_cases():
+    """(label, zones, pred, area) of the GPU tests that compare sums exactly."""
+    for n in (17, 64, 65, 1000):
+        for T in (47, 48, 65, 130, 132):
+            yield f"sweep n={n} T={T}", sc.sweep_zones(n, seed=n + T)[0], sc.make_pred_wide(n, T, seed=T), sc.make_area_wide(n, 8)
+    yield "windowing", sc.sweep_zones(1000, seed=77)[0] + sc.permutation_zone(1000), sc.make_pred_wide(1000, 48, seed=4), \
+        sc.make_area_wide(1000, 9)
+    yield "default slab", sc.default_slab_zones(), sc.make_pred_wide(sc.N_SLAB, 1032, seed=5), sc.make_area_wide(sc.N_SLAB, 6)
+    big = sc.make_pred_wide(sc.N_SLAB, 260, seed=7)[:, :, :68].contiguous()
+    yield "shrunk slab", sc.big_zones(), big, sc.make_area_wide(sc.N_SLAB, 6)
+    yield "floor slab", sc.big_zones(1), big, sc.make_area_wide(sc.N_SLAB, 6)
+
+
+def test_wide_data_is_order_sensitive():
+    """The condition that makes the exact comparisons of tests/test_gpu_series.py mean something:
+    in every zone of 16 entries or more, the same terms added in reversed list order, as a
+    balanced tree, and (three chunks or more: two chunk sums commute) with the chunk sums in
+    reversed order each differ from ``series_exact`` in a quarter of the steps or more.  The
+    sweep's cases with one row (every term of a zone is the same number: reversal cannot show) and
+    with T = 1 and 3 (no quarter to speak of) are left out.  The smallest fractions are printed."""
+    worst = {"reversed": 1.0, "pairwise": 1.0, "chunks reversed": 1.0}
+    several = 0
+    for label, zones, pred, area in _order_cases():
+        ptr, rows = zones.ptr.numpy(), zones.rows.numpy()
+        exact = sc.series_exact(pred, ptr, rows, area)["volume"]
+        for z in range(zones.num_zones):
+            m = int(ptr[z + 1] - ptr[z])
+            if m < 16:
+                continue
+            orders = {"reversed": sc.volume_reversed, "pairwise": sc.volume_pairwise}
+            if m > 2 * sc.CHUNK:
+                orders["chunks reversed"] = sc.volume_chunks_reversed
+                several += 1
+            for name, fn in orders.items():
+                f = sc.differing_fraction(fn(pred, ptr, rows, area, z), exact[z])
+                worst[name] = min(worst[name], f)
+                assert f >= 0.25, f"{label}: zone {z} of {m} entries, {name}: only {f:.0%} of the steps differ"
+    assert several >= 4
+    print("\nwide data, smallest fraction of steps that differ from the documented order: "
+          + ", ".join(f"{k} {v:.0%}" for k, v in worst.items()))
+
+
+def test_wide_areas_make_wet_area_order_sensitive():
+    """Areas over 1 .. 1e4 add exactly in any order in zones of this size, so the default data pin
+    the order of ``wet_area`` only in the million-entry zone.  With AREA_SPAN the condition above
+    holds for ``wet_area`` at threshold 0.0 in the zones of 255 entries and more of the default
+    slab set (a few 24-bit terms seldom round, whatever their spread: the small zones are left to
+    the volume)."""
+    zones = sc.default_slab_zones()
+    pred = sc.make_pred_wide(sc.N_SLAB, 48, seed=5)
+    ptr, rows = zones.ptr.numpy(), zones.rows.numpy()
+    narrow = sc.make_area_wide(sc.N_SLAB, 6)
+    wet = sc.wetness(pred, 0.0)
+    assert np.array_equal(sc.series_exact(pred, ptr, rows, narrow, (0.0,))["wet_area"][0],
+                          sc.series_exact(wet, ptr, rows, narrow)["volume"])
+    for z in range(zones.num_zones):
+        assert sc.differing_fraction(sc.volume_reversed(wet, ptr, rows, narrow, z),
+                                     sc.series_exact(wet, ptr, rows, narrow)["volume"][z]) == 0.0
+    area = sc.make_area_wide(sc.N_SLAB, 6, **sc.AREA_SPAN)
+    exact = sc.series_exact(pred, ptr, rows, area, (0.0,))["wet_area"][0]
+    for z in range(zones.num_zones):
+        m = int(ptr[z + 1] - ptr[z])
+        if m < 255:
+            continue
+        orders = [sc.volume_reversed, sc.volume_pairwise] + ([sc.volume_chunks_reversed] if m > 2 * sc.CHUNK else [])
+        for fn in orders:
+            f = sc.differing_fraction(fn(wet, ptr, rows, area, z), exact[z])
+            assert f >= 0.25, f"zone {z} of {m} entries, {fn.__name__}: only {f:.0%} of the steps differ"
+
+
+def test_census_of_steps_per_launch():
+    """The steps per launch S of the three multi-launch zone sets, recovered from the launch
+    query, and that every T the GPU tests run on them needs two launches or more."""
+    for name, (make, S, Ts) in sc.SLAB_SETS.items():
+        zones = make()
+        assert sc.steps_per_launch(zones) == S, name
+        assert all(T > S for T in Ts), name
+        assert zones.launch(S) == zones.launch(10 * S)              # a longer window launches no more at once
+        zones.close()
+    # exactly 4096 chunks: iters is the tiles of a launch
+    only = Zones.from_lists([torch.zeros(sc.BIG, dtype=torch.int64)], 1)
+    assert [only.launch(t)[2] for t in (64, 65, 128, 129, 5000)] == [1, 2, 2, 2, 2]
+    only.close()
