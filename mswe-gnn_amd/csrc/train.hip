@@ -200,32 +200,13 @@ __global__ __launch_bounds__(kGemmThreads) void k_gemm(GemmArgs a) {
 
 // out[i] = sum_{s < splits} part[s][i], i < count (fp64 partials, summed in fp64).  A
 // 256-thread workgroup owns 64 outputs; row group p (of 4) adds splits p, p + 4, ... in order,
-// then the 4 partials are added in order through LDS (fixed order: deterministic)
-__global__ __launch_bounds__(256) void k_sum_splits(const double* __restrict__ part, int splits, long count,
-                                                    float* __restrict__ out) {
+// then the 4 partials are added in order through LDS (fixed order: deterministic).  db != null:
+// the partials are [M][N1] with the bias gradient as their last column -- columns < N1 - 1 go to
+// out = dW [M][N1 - 1], the last to db [M]
+__global__ __launch_bounds__(256) void k_sum_splits(const double* __restrict__ part, int splits, long count, int N1,
+                                                    float* __restrict__ out, float* __restrict__ db) {
   __shared__ double red[4][64];
   const int c = threadIdx.x & 63, p = threadIdx.x >> 6;
-  for (long i0 = blockIdx.x * 64L; i0 < count; i0 += gridDim.x * 64L) {
-    const long i = i0 + c;
-    double v = 0.0;
-    if (i < count) {
-#pragma unroll 8
-      for (int s = p; s < splits; s += 4) v += part[(long)s * count + i];
-    }
-    red[p][c] = v;
-    __syncthreads();
-    if (p == 0 && i < count) out[i] = (float)(((red[0][c] + red[1][c]) + red[2][c]) + red[3][c]);
-    __syncthreads();
-  }
-}
-
-// k_sum_splits over [M][N1] partials whose last column is the bias gradient: columns < N1 - 1
-// go to dW [M][N1 - 1], the last to db [M]
-__global__ __launch_bounds__(256) void k_sum_splits_wb(const double* __restrict__ part, int splits, int M, int N1,
-                                                       float* __restrict__ dW, float* __restrict__ db) {
-  __shared__ double red[4][64];
-  const int c = threadIdx.x & 63, p = threadIdx.x >> 6;
-  const long count = (long)M * N1;
   for (long i0 = blockIdx.x * 64L; i0 < count; i0 += gridDim.x * 64L) {
     const long i = i0 + c;
     double v = 0.0;
@@ -237,10 +218,14 @@ __global__ __launch_bounds__(256) void k_sum_splits_wb(const double* __restrict_
     __syncthreads();
     if (p == 0 && i < count) {
       const float t = (float)(((red[0][c] + red[1][c]) + red[2][c]) + red[3][c]);
-      const long m = i / N1;
-      const int n = (int)(i - m * N1);
-      if (n < N1 - 1) dW[m * (N1 - 1) + n] = t;
-      else db[m] = t;
+      if (!db) {
+        out[i] = t;
+      } else {
+        const long m = i / N1;
+        const int n = (int)(i - m * N1);
+        if (n < N1 - 1) out[m * (N1 - 1) + n] = t;
+        else db[m] = t;
+      }
     }
     __syncthreads();
   }
@@ -518,51 +503,113 @@ inline int blocks_for(long n, int threads = 256) {
   return (int)std::max<long>(1, std::min<long>(b, 16384));
 }
 
-// split-K partial slices a weight gradient over R rows uses (weight_grad) -- also bounds the
+// k<<<blocks, 256, 0, st>>>(args...) and the launch's error
+template <typename K, typename... A>
+hipError_t launch(K k, int blocks, hipStream_t st, A... args) {
+  hipLaunchKernelGGL(k, dim3(blocks), dim3(256), 0, st, args...);
+  return hipGetLastError();
+}
+// a grid-stride elementwise kernel over n elements
+template <typename K, typename... A>
+hipError_t launch_n(K k, long n, hipStream_t st, A... args) {
+  return launch(k, blocks_for(n), st, args...);
+}
+
+#define CHECK(x)                       \
+  do {                                 \
+    hipError_t _e = (x);               \
+    if (_e != hipSuccess) return _e;   \
+  } while (0)
+
+// split-K partial slices a weight gradient over R rows asks for (weight_grad) -- also bounds the
 // column-sum slices of mlp_backward (ceil(R / max(256, R / kMaxSplits)) <= this)
 inline long splits_for(long R) { return std::min<long>(kMaxSplits, std::max<long>(1, R / (8 * kBK))); }
 
-struct Layout {  // float offsets into the saved / scratch buffers
-  long X0, pre[4], post[4], s, nrm, outk, agg, nz, saved;
-  long G0, G1, dagg, t, ds, dA, dB, part, spart, scratch;
+// The split-K geometry of a reduction over R rows: the slice length (whole K tiles) and the
+// slices that then hold rows -- fewer than asked for where the rounding up covers R sooner.
+// k_gemm's grid and k_sum_splits' slice count both come from here.
+struct SplitK {
+  int kchunk, used;
+};
+inline SplitK split_k(long R) {
+  const int K = (int)R, splits = (int)splits_for(R);
+  const int kchunk = ((K + splits - 1) / splits + kBK - 1) / kBK * kBK;
+  return SplitK{kchunk, std::max(1, (K + kchunk - 1) / kchunk)};
+}
+
+inline long al(long n) { return (n + 63) / 64 * 64; }  // every slot starts on a 64-float boundary
+
+// One make_mlp stack over `rows` rows: its widths and the float offsets of what it saves
+// (pre[0..L), then post[0..L) -- without post[L - 1] unless keep_last) and of its scratch (two
+// [rows][wmax] buffers, the fp64 split-K partials for split_rows rows, the fp64 slope partials).
+// The SWEGNN layout embeds one for its edge MLP.
+struct MlpLayout {
   int L, w[5], wmax;
+  bool keep_last;
+  long pre[4], post[4], saved;            // saved: the offset after the stack's saved slots
+  long A, B, part, spart, scratch;        // scratch: the offset after its scratch slots
 };
 
-bool layout_of(const msw_swegnn_train_desc* d, Layout& y) {
-  if (!d || d->n_layers < 1 || d->n_layers > 4 || d->F < 1 || d->K < 1 || d->K > kMaxHops || d->num_nodes < 0 ||
-      d->num_edges < 0 || d->edge_features < 0)
-    return false;
-  const long E = d->num_edges, N = d->num_nodes, F = d->F;
-  y.L = d->n_layers;
+// Validates n_layers / width[] and lays the stack out from the offsets saved0 / scratch0.
+bool stack_layout_of(int n_layers, const int32_t* width, long rows, bool keep_last, long split_rows, long saved0,
+                     long scratch0, MlpLayout& y) {
+  if (n_layers < 1 || n_layers > 4) return false;
+  y.L = n_layers;
+  y.keep_last = keep_last;
   y.wmax = 0;
   for (int l = 0; l <= y.L; ++l) {
-    y.w[l] = d->width[l];
+    y.w[l] = width[l];
     if (y.w[l] <= 0) return false;
     y.wmax = std::max(y.wmax, y.w[l]);
   }
-  if (y.w[0] != 4 * F + d->edge_features || y.w[y.L] != F) return false;
-  auto al = [](long n) { return (n + 63) / 64 * 64; };
+  long o = saved0;
+  for (int l = 0; l < y.L; ++l) { y.pre[l] = o; o += al(rows * y.w[l + 1]); }
+  for (int l = 0; l < (keep_last ? y.L : y.L - 1); ++l) { y.post[l] = o; o += al(rows * y.w[l + 1]); }
+  y.saved = o;
+  o = scratch0;
+  y.A = o; o += al(rows * y.wmax);
+  y.B = o; o += al(rows * y.wmax);
+  y.part = o; o += al(2L * splits_for(split_rows) * y.wmax * (y.wmax + 1));  // fp64 partials
+  y.spart = o; o += al(kMaxSplits * 4L);
+  y.scratch = o;
+  return true;
+}
+
+struct Layout {  // float offsets into the saved / scratch buffers of one SWEGNN layer
+  long X0, s, nrm, outk, agg, nz, saved;
+  long G0, G1, dagg, t, ds, scratch;
+  MlpLayout m;  // the edge MLP over the E edges: saved after X0, scratch after ds
+};
+
+bool layout_of(const msw_swegnn_train_desc* d, Layout& y) {
+  if (!d || d->F < 1 || d->K < 1 || d->K > kMaxHops || d->num_nodes < 0 || d->num_edges < 0 || d->edge_features < 0)
+    return false;
+  const long E = d->num_edges, N = d->num_nodes, F = d->F;
   long o = 0;
-  y.X0 = o; o += al(E * y.w[0]);
-  for (int l = 0; l < y.L; ++l) { y.pre[l] = o; o += al(E * y.w[l + 1]); }
-  for (int l = 0; l < y.L; ++l) { y.post[l] = o; o += al(E * y.w[l + 1]); }
+  y.G0 = o; o += al(N * F);
+  y.G1 = o; o += al(N * F);
+  y.dagg = o; o += al(N * F);
+  y.t = o; o += al(E * F);
+  y.ds = o; o += al(E * F);
+  y.X0 = 0;
+  if (!stack_layout_of(d->n_layers, d->width, E, true, std::max(E, N), al(E * d->width[0]), o, y.m)) return false;
+  if (y.m.w[0] != 4 * F + d->edge_features || y.m.w[y.m.L] != F) return false;
+  o = y.m.saved;
   y.s = o; o += al(E * F);
   y.nrm = o; o += al(E);
   y.outk = o; o += al((long)(d->K + 1) * N * F);
   y.agg = o; o += al((long)d->K * N * F);
   y.nz = o; o += al((long)d->K * N);
   y.saved = o;
-  o = 0;
-  y.G0 = o; o += al(N * F);
-  y.G1 = o; o += al(N * F);
-  y.dagg = o; o += al(N * F);
-  y.t = o; o += al(E * F);
-  y.ds = o; o += al(E * F);
-  y.dA = o; o += al(E * y.wmax);
-  y.dB = o; o += al(E * y.wmax);
-  y.part = o; o += al(2L * splits_for(std::max(E, N)) * y.wmax * (y.wmax + 1));  // fp64 partials
-  y.spart = o; o += al(kMaxSplits * 4L);
-  y.scratch = o;
+  y.scratch = y.m.scratch;
+  return true;
+}
+
+// msw_mlp_train_*: the stack alone, its output going to the caller's `out`
+bool mlp_layout_of(const msw_mlp_train_desc* d, MlpLayout& y) {
+  if (!d || d->rows < 0 || !stack_layout_of(d->n_layers, d->width, d->rows, false, d->rows, 0, 0, y)) return false;
+  for (int l = 0; l < y.L; ++l)
+    if (!d->weight[l]) return false;
   return true;
 }
 
@@ -576,51 +623,64 @@ struct MlpRun {
   const float* const* slope;
 };
 
-struct MlpLayout {  // float offsets: saved = pre[0..L-1], post[0..L-2]; scratch = A, B, partials
-  long pre[4], post[4], saved;
-  long A, B, part, spart, scratch;
-  int L, w[5], wmax;
-};
-
-bool mlp_layout_of(const msw_mlp_train_desc* d, MlpLayout& y) {
-  if (!d || d->n_layers < 1 || d->n_layers > 4 || d->rows < 0) return false;
-  const long R = d->rows;
-  y.L = d->n_layers;
-  y.wmax = 0;
-  for (int l = 0; l <= y.L; ++l) {
-    y.w[l] = d->width[l];
-    if (y.w[l] <= 0) return false;
-    y.wmax = std::max(y.wmax, y.w[l]);
-  }
-  for (int l = 0; l < y.L; ++l)
-    if (!d->weight[l]) return false;
-  auto al = [](long n) { return (n + 63) / 64 * 64; };
-  long o = 0;
-  for (int l = 0; l < y.L; ++l) { y.pre[l] = o; o += al(R * y.w[l + 1]); }
-  for (int l = 0; l + 1 < y.L; ++l) { y.post[l] = o; o += al(R * y.w[l + 1]); }
-  y.saved = o;
-  o = 0;
-  y.A = o; o += al(R * y.wmax);
-  y.B = o; o += al(R * y.wmax);
-  y.part = o; o += al(2L * splits_for(R) * y.wmax * (y.wmax + 1));  // fp64 partials
-  y.spart = o; o += al(kMaxSplits * 4L);
-  y.scratch = o;
-  return true;
-}
-
-MlpRun mlp_of(const msw_swegnn_train_desc* d, const Layout& y, long rows) {
+template <typename Desc>  // either training descriptor: both name act / weight / bias / slope alike
+MlpRun mlp_run(const Desc* d, const MlpLayout& y, long rows) {
   return MlpRun{rows, y.L, y.w, d->act, d->weight, d->bias, d->slope};
 }
 
-hipError_t gemm(const GemmArgs& a0, hipStream_t st, int splits = 1) {
-  GemmArgs a = a0;
-  dim3 grid((a.M + kBM - 1) / kBM, (a.N + kBN - 1) / kBN, 1);
-  if (a.part) {
-    splits = std::max(1, std::min(splits, kMaxSplits));
-    a.kchunk = ((a.K + splits - 1) / splits + kBK - 1) / kBK * kBK;
-    grid.z = (a.K + a.kchunk - 1) / a.kchunk;
-    if (grid.z == 0) grid.z = 1;
+// pre[l] / post[l] of a stack saved at `base`; `last` stands for the last layer's output where
+// the layout does not keep it (the caller's `out` in the forward, nothing in the backward)
+template <typename T>
+struct StackPtrs {
+  T* pre[4];
+  T* post[4];
+};
+template <typename T>
+StackPtrs<T> stack_ptrs(T* base, const MlpLayout& y, T* last = nullptr) {
+  StackPtrs<T> p{};
+  for (int l = 0; l < y.L; ++l) {
+    p.pre[l] = base + y.pre[l];
+    p.post[l] = y.keep_last || l + 1 < y.L ? base + y.post[l] : last;
   }
+  return p;
+}
+
+// no rows reach the stack (an empty row set, a graph without edges): every parameter gradient is zero
+hipError_t zero_param_grads(const MlpLayout& y, float* const* dW, float* const* db, float* const* dslope,
+                            hipStream_t st) {
+  for (int l = 0; l < y.L; ++l) {
+    if (dW[l]) CHECK(hipMemsetAsync(dW[l], 0, sizeof(float) * y.w[l] * y.w[l + 1], st));
+    if (db[l]) CHECK(hipMemsetAsync(db[l], 0, sizeof(float) * y.w[l + 1], st));
+    if (dslope[l]) CHECK(hipMemsetAsync(dslope[l], 0, sizeof(float), st));
+  }
+  return hipSuccess;
+}
+
+// The two shapes of a linear layer besides its weight gradient, with k_gemm's strides
+// (A(m, k) = A[m lam + k lak], B(k, n) = B[k lbk + n lbn]) set; the caller adds its epilogue
+// (bias, pre, act / slope, addend -- pre and addend are [rows][out] like C).
+// C [rows][out] = X [rows][in] W^T, W [out][in]: B(k, n) = W[n][k]
+GemmArgs gemm_xwt(long rows, int in, int out, const float* X, const float* W, float* C) {
+  GemmArgs g{};
+  g.M = (int)rows; g.N = out; g.K = in;
+  g.A = X; g.lam = in; g.lak = 1;
+  g.B = W; g.lbk = 1; g.lbn = in;
+  g.C = C; g.ldc = g.ldp = g.ldd = out;
+  return g;
+}
+// C [rows][in] = dY [rows][out] W, W [out][in]: B(k, n) = W[k][n]
+GemmArgs gemm_dyw(long rows, int out, int in, const float* dY, const float* W, float* C) {
+  GemmArgs g{};
+  g.M = (int)rows; g.N = in; g.K = out;
+  g.A = dY; g.lam = out; g.lak = 1;
+  g.B = W; g.lbk = in; g.lbn = 1;
+  g.C = C; g.ldc = in;
+  return g;
+}
+
+// slices: the split-K slices of a.part (a.kchunk rows each, split_k)
+hipError_t gemm(const GemmArgs& a, hipStream_t st, int slices = 1) {
+  const dim3 grid((a.M + kBM - 1) / kBM, (a.N + kBN - 1) / kBN, slices);
   if (a.part)
     hipLaunchKernelGGL(k_gemm<true>, grid, dim3(kGemmThreads), 0, st, a);
   else
@@ -628,30 +688,26 @@ hipError_t gemm(const GemmArgs& a0, hipStream_t st, int splits = 1) {
   return hipGetLastError();
 }
 
+// out [count] (db: dW [M][N1 - 1] and db [M], k_sum_splits) = the sum of `splits` fp64 partials
+hipError_t sum_splits(const double* part, int splits, long count, float* out, hipStream_t st, int N1 = 0,
+                      float* db = nullptr) {
+  return launch(k_sum_splits, blocks_for(count, 64), st, part, splits, count, N1, out, db);
+}
+
 // dW [M][N] = sum_rows A(row, m) B(row, n): split-K over the rows, partials summed in order
 // db (nullable) [M] = sum_rows A(row, m): the same GEMM against an implicit ones column of B
 // (part: [splits][M][N (+ 1)] doubles)
 hipError_t weight_grad(const float* A, int lda, const float* B, int ldb, long R, int M, int N, float* part,
                        float* dW, hipStream_t st, float* db = nullptr) {
+  const SplitK sk = split_k(R);
   GemmArgs g{};
   g.M = M; g.N = db ? N + 1 : N; g.K = (int)R;
   g.A = A; g.lam = 1; g.lak = lda;
   g.B = B; g.lbk = ldb; g.lbn = 1;
-  g.part = part;
+  g.part = part; g.kchunk = sk.kchunk;
   g.bones = db ? 1 : 0;
-  const int splits = (int)splits_for(R);
-  hipError_t e = gemm(g, st, splits);
-  if (e != hipSuccess) return e;
-  const int kchunk = ((g.K + splits - 1) / splits + kBK - 1) / kBK * kBK;
-  const int used = std::max(1, (g.K + kchunk - 1) / kchunk);
-  const double* p64 = reinterpret_cast<const double*>(part);
-  if (db)
-    hipLaunchKernelGGL(k_sum_splits_wb, dim3(blocks_for((long)M * g.N, 64)), dim3(256), 0, st, p64, used, M, g.N, dW,
-                       db);
-  else
-    hipLaunchKernelGGL(k_sum_splits, dim3(blocks_for((long)M * N, 64)), dim3(256), 0, st, p64, used, (long)M * N,
-                       dW);
-  return hipGetLastError();
+  CHECK(gemm(g, st, sk.used));
+  return sum_splits(reinterpret_cast<const double*>(part), sk.used, (long)M * g.N, dW, st, g.N, db);
 }
 
 // One make_mlp stack (models/models.py:121-146: Linear + activation after every layer) over R
@@ -662,16 +718,11 @@ hipError_t weight_grad(const float* A, int lda, const float* B, int ldb, long R,
 hipError_t mlp_forward(const MlpRun& m, const float* X, float* const* pre, float* const* post, hipStream_t st) {
   const float* in = X;
   for (int l = 0; l < m.L; ++l) {
-    GemmArgs g{};
-    g.M = (int)m.R; g.N = m.w[l + 1]; g.K = m.w[l];
-    g.A = in; g.lam = m.w[l]; g.lak = 1;
-    g.B = m.W[l]; g.lbk = 1; g.lbn = m.w[l];  // B(k, n) = W[n][k]
-    g.C = post[l]; g.ldc = m.w[l + 1];
+    GemmArgs g = gemm_xwt(m.R, m.w[l], m.w[l + 1], in, m.W[l], post[l]);
     g.bias = m.b[l];
-    g.pre = pre[l]; g.ldp = m.w[l + 1];
+    g.pre = pre[l];
     g.act = m.act[l]; g.slope = m.slope[l];
-    hipError_t e = gemm(g, st);
-    if (e != hipSuccess) return e;
+    CHECK(gemm(g, st));
     in = post[l];
   }
   return hipSuccess;
@@ -692,30 +743,19 @@ hipError_t mlp_backward(const MlpRun& m, const float* X, const float* const* pre
   for (int l = m.L - 1; l >= 0; --l) {
     const int wi = m.w[l], wo = m.w[l + 1];
     const int ab = blocks_for(R * wo) < kMaxSplits ? blocks_for(R * wo) : kMaxSplits;
-    hipLaunchKernelGGL(k_act_bwd, dim3(ab), dim3(256), 0, st, pre[l], dcur, R * wo, m.act[l], m.slope[l], dpre, sp64);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    if (dslope[l]) hipLaunchKernelGGL(k_sum_splits, dim3(1), dim3(256), 0, st, sp64, ab, 1L, dslope[l]);
+    CHECK(launch(k_act_bwd, ab, st, pre[l], dcur, R * wo, m.act[l], m.slope[l], dpre, sp64));
+    if (dslope[l]) CHECK(sum_splits(sp64, ab, 1, dslope[l], st));
     // the bias gradient rides on the weight-gradient GEMM as an extra ones column of X where
     // that column fits the last 64-wide output tile; else its own column sums
     const bool fuse_db = db[l] && dW[l] && wi % kBN != 0;
     if (db[l] && !fuse_db) {
-      hipLaunchKernelGGL(k_colsum, dim3(nrs), dim3(256), 0, st, dpre, R, wo, rchunk, p64);
-      hipLaunchKernelGGL(k_sum_splits, dim3(blocks_for(wo, 64)), dim3(256), 0, st, p64, nrs, (long)wo, db[l]);
+      CHECK(launch(k_colsum, nrs, st, dpre, R, wo, rchunk, p64));
+      CHECK(sum_splits(p64, nrs, wo, db[l], st));
     }
-    if ((e = hipGetLastError()) != hipSuccess) return e;
     const float* Xl = l == 0 ? X : post[l - 1];
-    if (dW[l] && (e = weight_grad(dpre, wo, Xl, wi, R, wo, wi, part, dW[l], st, fuse_db ? db[l] : nullptr)) != hipSuccess)
-      return e;
+    if (dW[l]) CHECK(weight_grad(dpre, wo, Xl, wi, R, wo, wi, part, dW[l], st, fuse_db ? db[l] : nullptr));
     float* tgt = l == 0 ? dX : bufA;
-    if (tgt) {
-      GemmArgs g{};  // d X_l = dpre W_l
-      g.M = (int)R; g.N = wi; g.K = wo;
-      g.A = dpre; g.lam = wo; g.lak = 1;
-      g.B = m.W[l]; g.lbk = wi; g.lbn = 1;
-      g.C = tgt; g.ldc = wi;
-      if ((e = gemm(g, st)) != hipSuccess) return e;
-    }
+    if (tgt) CHECK(gemm(gemm_dyw(R, wo, wi, dpre, m.W[l], tgt), st));  // d X_l = dpre W_l
     dcur = bufA;
   }
   return hipSuccess;
@@ -754,29 +794,15 @@ int msw_swegnn_train_forward(const msw_swegnn_train_desc* d, const float* xs, co
   const int F = d->F;
   float* X0 = saved + y.X0;
   if (E > 0) {
-    hipLaunchKernelGGL(k_gather_cat, dim3(blocks_for(E * y.w[0])), dim3(256), 0, st, d->row, d->col, xs, xd, ea, F,
-                       d->edge_features, E, X0);
-    TRY(hipGetLastError());
-    float* pre[4];
-    float* post[4];
-    for (int l = 0; l < y.L; ++l) {
-      pre[l] = saved + y.pre[l];
-      post[l] = saved + y.post[l];
-    }
-    TRY(mlp_forward(mlp_of(d, y, E), X0, pre, post, st));
-    hipLaunchKernelGGL(k_normalize, dim3(blocks_for(E)), dim3(256), 0, st, saved + y.post[y.L - 1], F, E, d->normalize,
-                       saved + y.s, saved + y.nrm);
-    TRY(hipGetLastError());
+    TRY(launch_n(k_gather_cat, E * y.m.w[0], st, d->row, d->col, xs, xd, ea, F, d->edge_features, E, X0));
+    const StackPtrs<float> p = stack_ptrs(saved, y.m);
+    TRY(mlp_forward(mlp_run(d, y.m, E), X0, p.pre, p.post, st));
+    TRY(launch_n(k_normalize, E, st, p.post[y.m.L - 1], F, E, d->normalize, saved + y.s, saved + y.nrm));
   }
   // out_0 = filter_matrix[0] x_d (gnn.py:401-404)
   float* o0 = saved + y.outk;
   if (d->with_filter_matrix) {
-    GemmArgs g{};
-    g.M = (int)N; g.N = F; g.K = F;
-    g.A = xd; g.lam = F; g.lak = 1;
-    g.B = d->filter[0]; g.lbk = 1; g.lbn = F;
-    g.C = o0; g.ldc = F;
-    TRY(gemm(g, st));
+    TRY(gemm(gemm_xwt(N, F, F, xd, d->filter[0], o0), st));
   } else {
     TRY(hipMemcpyAsync(o0, xd, sizeof(float) * N * F, hipMemcpyDeviceToDevice, st));
   }
@@ -785,21 +811,15 @@ int msw_swegnn_train_forward(const msw_swegnn_train_desc* d, const float* xs, co
     float* on = k + 1 == d->K ? out : saved + y.outk + (long)(k + 1) * N * F;  // out_K is not needed later
     float* agg = saved + y.agg + (long)k * N * F;
     int* nz = reinterpret_cast<int*>(saved + y.nz + (long)k * N);
-    hipLaunchKernelGGL(k_node_nz, dim3(blocks_for(N)), dim3(256), 0, st, ok, F, N, nz);
-    hipLaunchKernelGGL(k_hop_agg, dim3(blocks_for(N * F)), dim3(256), 0, st, d->in_ptr, d->in_edge, d->row, ok,
-                       saved + y.s, nz, F, N, d->with_gradient, d->upwind_mode, agg);
-    TRY(hipGetLastError());
+    TRY(launch_n(k_node_nz, N, st, ok, F, N, nz));
+    TRY(launch_n(k_hop_agg, N * F, st, d->in_ptr, d->in_edge, d->row, ok, saved + y.s, nz, F, N, d->with_gradient,
+                 d->upwind_mode, agg));
     if (d->with_filter_matrix) {  // out_{k+1} = out_k + filter_matrix[k+1](agg)
-      GemmArgs g{};
-      g.M = (int)N; g.N = F; g.K = F;
-      g.A = agg; g.lam = F; g.lak = 1;
-      g.B = d->filter[k + 1]; g.lbk = 1; g.lbn = F;
-      g.C = on; g.ldc = F;
-      g.addend = ok; g.ldd = F;
+      GemmArgs g = gemm_xwt(N, F, F, agg, d->filter[k + 1], on);
+      g.addend = ok;
       TRY(gemm(g, st));
     } else {
-      hipLaunchKernelGGL(k_add, dim3(blocks_for(N * F)), dim3(256), 0, st, ok, agg, N * F, on);
-      TRY(hipGetLastError());
+      TRY(launch_n(k_add, N * F, st, ok, agg, N * F, on));
     }
   }
   return MSW_OK;
@@ -823,7 +843,7 @@ int msw_swegnn_train_backward(const msw_swegnn_train_desc* d, const float* xs, c
   float* dagg = scratch + y.dagg;
   float* t = scratch + y.t;
   float* ds = scratch + y.ds;
-  float* part = scratch + y.part;
+  float* part = scratch + y.m.part;
   if (E > 0) TRY(hipMemsetAsync(ds, 0, sizeof(float) * E * F, st));
   for (int k = d->K - 1; k >= 0; --k) {
     const float* ok = saved + y.outk + (long)k * N * F;
@@ -831,75 +851,41 @@ int msw_swegnn_train_backward(const msw_swegnn_train_desc* d, const float* xs, c
     const int* nz = reinterpret_cast<const int*>(saved + y.nz + (long)k * N);
     if (d->with_filter_matrix) {
       if (gr->d_filter[k + 1]) TRY(weight_grad(G, F, agg, F, N, F, F, part, gr->d_filter[k + 1], st));
-      GemmArgs g{};  // dagg = G W_{k+1}
-      g.M = (int)N; g.N = F; g.K = F;
-      g.A = G; g.lam = F; g.lak = 1;
-      g.B = d->filter[k + 1]; g.lbk = F; g.lbn = 1;
-      g.C = dagg; g.ldc = F;
-      TRY(gemm(g, st));
+      TRY(gemm(gemm_dyw(N, F, F, G, d->filter[k + 1], dagg), st));  // dagg = G W_{k+1}
     }
     const float* dg = d->with_filter_matrix ? dagg : G;  // no filter: dagg = G
-    if (E > 0) {
-      hipLaunchKernelGGL(k_edge_bwd, dim3(blocks_for(E * F)), dim3(256), 0, st, d->row, d->col, ok, saved + y.s, nz,
-                         dg, F, E, d->with_gradient, d->upwind_mode, ds, t);
-      TRY(hipGetLastError());
-    }
+    if (E > 0)
+      TRY(launch_n(k_edge_bwd, E * F, st, d->row, d->col, ok, saved + y.s, nz, dg, F, E, d->with_gradient,
+                   d->upwind_mode, ds, t));
     float* Gn = Gbuf[gi];
     gi ^= 1;
-    hipLaunchKernelGGL(k_node_bwd, dim3(blocks_for(N * F)), dim3(256), 0, st, d->in_ptr, d->in_edge, d->out_ptr,
-                       d->out_edge, G, t, F, N, d->with_gradient, Gn);
-    TRY(hipGetLastError());
+    TRY(launch_n(k_node_bwd, N * F, st, d->in_ptr, d->in_edge, d->out_ptr, d->out_edge, G, t, F, N, d->with_gradient,
+                 Gn));
     G = Gn;
   }
   // out_0 = W_0 x_d
   if (d->with_filter_matrix) {
     if (gr->d_filter[0]) TRY(weight_grad(G, F, xd, F, N, F, F, part, gr->d_filter[0], st));
-    GemmArgs g{};
-    g.M = (int)N; g.N = F; g.K = F;
-    g.A = G; g.lam = F; g.lak = 1;
-    g.B = d->filter[0]; g.lbk = F; g.lbn = 1;
-    g.C = gr->d_x_d; g.ldc = F;
-    TRY(gemm(g, st));
+    TRY(gemm(gemm_dyw(N, F, F, G, d->filter[0], gr->d_x_d), st));
   } else {
     TRY(hipMemcpyAsync(gr->d_x_d, G, sizeof(float) * N * F, hipMemcpyDeviceToDevice, st));
   }
-  if (E == 0) {
+  if (E == 0) {  // no edges: nothing reaches the edge MLP or x_s
     if (gr->d_x_s) TRY(hipMemsetAsync(gr->d_x_s, 0, sizeof(float) * N * F, st));
-    for (int l = 0; l < y.L; ++l) {
-      if (gr->d_weight[l]) TRY(hipMemsetAsync(gr->d_weight[l], 0, sizeof(float) * y.w[l] * y.w[l + 1], st));
-      if (gr->d_bias[l]) TRY(hipMemsetAsync(gr->d_bias[l], 0, sizeof(float) * y.w[l + 1], st));
-      if (gr->d_slope[l]) TRY(hipMemsetAsync(gr->d_slope[l], 0, sizeof(float), st));
-    }
+    TRY(zero_param_grads(y.m, gr->d_weight, gr->d_bias, gr->d_slope, st));
     return MSW_OK;
   }
   // s = normalize(h): ds -> dh
-  float* dcur = scratch + y.dA;
-  float* dpre = scratch + y.dB;
-  hipLaunchKernelGGL(k_normalize_bwd, dim3(blocks_for(E)), dim3(256), 0, st, saved + y.s, saved + y.nrm, ds, F, E,
-                     d->normalize, dcur);
-  TRY(hipGetLastError());
-  {
-    const float* pre[4];
-    const float* post[4];
-    for (int l = 0; l < y.L; ++l) {
-      pre[l] = saved + y.pre[l];
-      post[l] = saved + y.post[l];
-    }
-    float* dW[4] = {gr->d_weight[0], gr->d_weight[1], gr->d_weight[2], gr->d_weight[3]};
-    float* db[4] = {gr->d_bias[0], gr->d_bias[1], gr->d_bias[2], gr->d_bias[3]};
-    float* dsl[4] = {gr->d_slope[0], gr->d_slope[1], gr->d_slope[2], gr->d_slope[3]};
-    TRY(mlp_backward(mlp_of(d, y, E), saved + y.X0, pre, post, dcur, dcur, dW, db, dsl, dcur, dpre, part,
-                     scratch + y.spart, st));
-  }
+  float* dcur = scratch + y.m.A;
+  TRY(launch_n(k_normalize_bwd, E, st, saved + y.s, saved + y.nrm, ds, F, E, d->normalize, dcur));
+  const StackPtrs<const float> p = stack_ptrs(saved, y.m);
+  TRY(mlp_backward(mlp_run(d, y.m, E), saved + y.X0, p.pre, p.post, dcur, dcur, gr->d_weight, gr->d_bias, gr->d_slope,
+                   dcur, scratch + y.m.B, part, scratch + y.m.spart, st));
   // dcur = dX0 [E][4F + ef]
-  hipLaunchKernelGGL(k_scatter_inputs, dim3(blocks_for(N * F)), dim3(256), 0, st, d->in_ptr, d->in_edge, d->out_ptr,
-                     d->out_edge, dcur, F, d->edge_features, N, gr->d_x_s, gr->d_x_d);
-  TRY(hipGetLastError());
-  if (d->edge_features > 0 && gr->d_edge_attr) {
-    hipLaunchKernelGGL(k_copy_cols, dim3(blocks_for(E * d->edge_features)), dim3(256), 0, st, dcur, E, y.w[0], 4 * F,
-                       d->edge_features, gr->d_edge_attr);
-    TRY(hipGetLastError());
-  }
+  TRY(launch_n(k_scatter_inputs, N * F, st, d->in_ptr, d->in_edge, d->out_ptr, d->out_edge, dcur, F, d->edge_features,
+               N, gr->d_x_s, gr->d_x_d));
+  if (d->edge_features > 0 && gr->d_edge_attr)
+    TRY(launch_n(k_copy_cols, E * d->edge_features, st, dcur, E, y.m.w[0], 4 * F, d->edge_features, gr->d_edge_attr));
   return MSW_OK;
 }
 
@@ -916,14 +902,8 @@ int msw_mlp_train_forward(const msw_mlp_train_desc* d, const float* x, float* sa
   if (!mlp_layout_of(d, y)) return set_error(MSW_ERR_INVALID, "inconsistent MLP training descriptor");
   if (d->rows == 0) return MSW_OK;
   if (!x || !saved || !out) return set_error(MSW_ERR_INVALID, "null argument");
-  float* pre[4];
-  float* post[4];
-  for (int l = 0; l < y.L; ++l) {
-    pre[l] = saved + y.pre[l];
-    post[l] = l + 1 < y.L ? saved + y.post[l] : out;
-  }
-  TRY(mlp_forward(MlpRun{d->rows, y.L, y.w, d->act, d->weight, d->bias, d->slope}, x, pre, post,
-                  (hipStream_t)stream));
+  const StackPtrs<float> p = stack_ptrs(saved, y, out);
+  TRY(mlp_forward(mlp_run(d, y, d->rows), x, p.pre, p.post, (hipStream_t)stream));
   return MSW_OK;
 }
 
@@ -933,26 +913,14 @@ int msw_mlp_train_backward(const msw_mlp_train_desc* d, const float* x, const fl
   if (!mlp_layout_of(d, y)) return set_error(MSW_ERR_INVALID, "inconsistent MLP training descriptor");
   if (!gr) return set_error(MSW_ERR_INVALID, "null argument");
   hipStream_t st = (hipStream_t)stream;
-  float* dW[4] = {gr->d_weight[0], gr->d_weight[1], gr->d_weight[2], gr->d_weight[3]};
-  float* db[4] = {gr->d_bias[0], gr->d_bias[1], gr->d_bias[2], gr->d_bias[3]};
-  float* dsl[4] = {gr->d_slope[0], gr->d_slope[1], gr->d_slope[2], gr->d_slope[3]};
-  if (d->rows == 0) {  // no rows: every gradient is zero
-    for (int l = 0; l < y.L; ++l) {
-      if (dW[l]) TRY(hipMemsetAsync(dW[l], 0, sizeof(float) * y.w[l] * y.w[l + 1], st));
-      if (db[l]) TRY(hipMemsetAsync(db[l], 0, sizeof(float) * y.w[l + 1], st));
-      if (dsl[l]) TRY(hipMemsetAsync(dsl[l], 0, sizeof(float), st));
-    }
+  if (d->rows == 0) {
+    TRY(zero_param_grads(y, gr->d_weight, gr->d_bias, gr->d_slope, st));
     return MSW_OK;
   }
   if (!x || !saved || !grad_out || !scratch) return set_error(MSW_ERR_INVALID, "null argument");
-  const float* pre[4];
-  const float* post[4];
-  for (int l = 0; l < y.L; ++l) {
-    pre[l] = saved + y.pre[l];
-    post[l] = l + 1 < y.L ? saved + y.post[l] : nullptr;  // the output is not needed
-  }
-  TRY(mlp_backward(MlpRun{d->rows, y.L, y.w, d->act, d->weight, d->bias, d->slope}, x, pre, post, grad_out,
-                   gr->d_x, dW, db, dsl, scratch + y.A, scratch + y.B, scratch + y.part, scratch + y.spart, st));
+  const StackPtrs<const float> p = stack_ptrs(saved, y);  // the output is not needed
+  TRY(mlp_backward(mlp_run(d, y, d->rows), x, p.pre, p.post, grad_out, gr->d_x, gr->d_weight, gr->d_bias, gr->d_slope,
+                   scratch + y.A, scratch + y.B, scratch + y.part, scratch + y.spart, st));
   return MSW_OK;
 }
 
@@ -961,9 +929,7 @@ int msw_pool_mean_forward(int64_t num_nodes, int32_t F, const int32_t* fine, con
   if (num_nodes < 0 || F < 1) return set_error(MSW_ERR_INVALID, "bad pooling sizes");
   if (num_nodes == 0) return MSW_OK;
   if (!fine || !cptr || !cedge || !x || !out) return set_error(MSW_ERR_INVALID, "null argument");
-  hipLaunchKernelGGL(k_pool_fwd, dim3(blocks_for(num_nodes * F)), dim3(256), 0, (hipStream_t)stream, cptr, cedge,
-                     fine, x, F, (long)num_nodes, out);
-  TRY(hipGetLastError());
+  TRY(launch_n(k_pool_fwd, num_nodes * F, (hipStream_t)stream, cptr, cedge, fine, x, F, (long)num_nodes, out));
   return MSW_OK;
 }
 
@@ -973,9 +939,8 @@ int msw_pool_mean_backward(int64_t num_nodes, int32_t F, const int32_t* coarse, 
   if (num_nodes < 0 || F < 1) return set_error(MSW_ERR_INVALID, "bad pooling sizes");
   if (num_nodes == 0) return MSW_OK;
   if (!coarse || !cptr || !fptr || !fedge || !grad_out || !grad_x) return set_error(MSW_ERR_INVALID, "null argument");
-  hipLaunchKernelGGL(k_pool_bwd, dim3(blocks_for(num_nodes * F)), dim3(256), 0, (hipStream_t)stream, fptr, fedge,
-                     coarse, cptr, grad_out, F, (long)num_nodes, grad_x);
-  TRY(hipGetLastError());
+  TRY(launch_n(k_pool_bwd, num_nodes * F, (hipStream_t)stream, fptr, fedge, coarse, cptr, grad_out, F, (long)num_nodes,
+               grad_x));
   return MSW_OK;
 }
 

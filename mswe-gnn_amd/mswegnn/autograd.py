@@ -51,35 +51,54 @@ RECORD = None
 
 
 def _al(n):
-    return (n + 63) // 64 * 64  # csrc/train.hip layout_of / mlp_layout_of: 64-float aligned slots
+    return (n + 63) // 64 * 64  # csrc/train.hip al(): every slot starts on a 64-float boundary
+
+
+# The saved buffers, restated from csrc/train.hip as float offsets (tests/test_host_cpu.py holds
+# each "end" against msw_*_train_workspace's saved_floats).
+def _stack_offsets(d, rows, o, keep_last):
+    """stack_layout_of: pre[0..L), then post[0..L) -- without the last layer's output unless
+    keep_last -- from offset o."""
+    off = {"pre": [], "post": []}
+    for name, n in (("pre", d.n_layers), ("post", d.n_layers if keep_last else d.n_layers - 1)):
+        for l in range(n):
+            off[name].append(o)
+            o += _al(rows * d.width[l + 1])
+    off["end"] = o
+    return off
+
+
+def _mlp_offsets(d):
+    """msw_mlp_train_forward's saved buffer (mlp_layout_of): the stack alone."""
+    return _stack_offsets(d, d.rows, 0, False)
+
+
+def _swegnn_offsets(d):
+    """msw_swegnn_train_forward's saved buffer (layout_of): X0, the edge MLP's stack, then s, nrm,
+    outk, agg, nz."""
+    E, N, F, K = d.num_edges, d.num_nodes, d.F, d.K
+    off = _stack_offsets(d, E, _al(E * d.width[0]), True)
+    o = off["end"]
+    for name, n in (("s", E * F), ("nrm", E), ("outk", (K + 1) * N * F), ("agg", K * N * F), ("nz", K * N)):
+        off[name] = o
+        o += _al(n)
+    off["X0"], off["end"] = 0, o
+    return off
+
+
+def _pre_signs(d, saved, rows, off):
+    return [saved[o:o + rows * d.width[l + 1]].view(rows, d.width[l + 1]) > 0 for l, o in enumerate(off["pre"])]
 
 
 def _swegnn_decisions(d, saved):
-    """The saved buffer of msw_swegnn_train_forward (csrc/train.hip layout_of): X0, pre[l],
-    post[l], s, nrm, outk, agg, nz -> {pre: [E x w(l+1) bool], nz: [K x N bool]}."""
-    E, N, F, K, nl = d.num_edges, d.num_nodes, d.F, d.K, d.n_layers
-    w = [d.width[i] for i in range(nl + 1)]
-    o = _al(E * w[0])
-    pre = []
-    for l in range(nl):
-        pre.append(saved[o:o + E * w[l + 1]].view(E, w[l + 1]) > 0)
-        o += _al(E * w[l + 1])
-    for l in range(nl):
-        o += _al(E * w[l + 1])
-    o += _al(E * F) + _al(E) + _al((K + 1) * N * F) + _al(K * N * F)
-    nz = saved[o:o + K * N].view(torch.int32).view(K, N) != 0
-    return {"kind": "swegnn", "pre": pre, "nz": [nz[k] for k in range(K)]}
+    """-> {pre: [E x w(l+1) bool], nz: [K x N bool]} read from the saved buffer."""
+    off, K, N = _swegnn_offsets(d), d.K, d.num_nodes
+    nz = saved[off["nz"]:off["nz"] + K * N].view(torch.int32).view(K, N) != 0
+    return {"kind": "swegnn", "pre": _pre_signs(d, saved, d.num_edges, off), "nz": [nz[k] for k in range(K)]}
 
 
 def _mlp_decisions(d, saved):
-    """The saved buffer of msw_mlp_train_forward (mlp_layout_of): pre[l], post[l]."""
-    R, nl = d.rows, d.n_layers
-    o, pre = 0, []
-    for l in range(nl):
-        w = d.width[l + 1]
-        pre.append(saved[o:o + R * w].view(R, w) > 0)
-        o += _al(R * w)
-    return {"kind": "mlp", "pre": pre}
+    return {"kind": "mlp", "pre": _pre_signs(d, saved, d.rows, _mlp_offsets(d))}
 
 
 class GraphCSR:
@@ -189,71 +208,91 @@ def supported(layer, x_s, x_d, edge_attr):
     return all(p.dtype == torch.float32 and p.is_cuda for p in layer.parameters())
 
 
+def _slots(mods, layer=None):
+    """(descriptor field, index, parameter) of every parameter a descriptor binds, in binding
+    order = the order of the Functions' *params: per Linear of the module sequence `mods` its
+    weight, its bias if it has one and the slope of a PReLU behind it, then `layer`'s K + 1 filter
+    matrices if it has them.  The one walk: descriptors, gradient structs and the cache
+    validation all go by it."""
+    i = -1
+    for m in mods:
+        if isinstance(m, nn.Linear):
+            i += 1
+            yield "weight", i, m.weight
+            if m.bias is not None:
+                yield "bias", i, m.bias
+        elif isinstance(m, nn.PReLU):
+            yield "slope", i, m.weight
+    if layer is not None and layer.with_filter_matrix:
+        for k, f in enumerate(layer.filter_matrix):
+            yield "filter", k, f.weight
+
+
 def _param_list(layer=None, seq=None):
     """The parameter objects a descriptor binds, in its order (cache validation)."""
-    out = []
-    for m in (layer.edge_mlp if layer is not None else seq):
-        if isinstance(m, nn.Linear):
-            out.append(m.weight)
-            if m.bias is not None:
-                out.append(m.bias)
-        elif isinstance(m, nn.PReLU):
-            out.append(m.weight)
-    if layer is not None and layer.with_filter_matrix:
-        out += [f.weight for f in layer.filter_matrix]
-    return out
+    return [p for _, _, p in _slots(layer.edge_mlp if layer is not None else seq, layer)]
 
 
-class _Meta:
-    """Everything but the tensors autograd tracks: the descriptor template of one call."""
+class _StackMeta:
+    """One make_mlp stack described once, from _mlp_layers(seq): the width / act fill of either
+    descriptor type, the parameter objects in binding order, their binding into the descriptor
+    and of their gradients into either grads struct, and the workspace sizes.  With the
+    descriptor `desc` it is everything but the tensors autograd tracks: the template of one
+    call."""
+
+    def __init__(self, layers, desc, workspace, layer=None):
+        self.layers, self.desc, self.workspace, self.ws = layers, desc, workspace, None
+        desc.n_layers = len(layers)
+        desc.width[0] = layers[0][0].in_features
+        for i, (lin, act) in enumerate(layers):
+            desc.width[i + 1] = lin.out_features
+            desc.act[i] = _act_code(act)
+        slots = list(_slots((m for pair in layers for m in pair), layer))
+        self.slots = [(field, i) for field, i, _ in slots]
+        self.params = [p for _, _, p in slots]
+
+    def bind(self, params):
+        """Point the descriptor at the (contiguous) parameter tensors of this call."""
+        for (field, i), p in zip(self.slots, params):
+            getattr(self.desc, field)[i] = p.data_ptr()
+        return self.desc
+
+    def bind_grads(self, g, grads):
+        """Point the grads struct at the gradient tensors (None: not wanted) of this call."""
+        for (field, i), t in zip(self.slots, grads):
+            getattr(g, "d_" + field)[i] = t.data_ptr() if t is not None else None
+
+    def sizes(self):
+        """(saved, scratch) floats: they depend on the descriptor's sizes only, asked once."""
+        if self.ws is None:
+            s, t = C.c_int64(), C.c_int64()
+            L.check(getattr(L.lib(), self.workspace)(C.byref(self.desc), C.byref(s), C.byref(t)))
+            self.ws = int(s.value), int(t.value)
+        return self.ws
+
+
+class _Meta(_StackMeta):
+    """A SWEGNN layer's call: its edge MLP's stack, the graph, the flags and the filters."""
 
     def __init__(self, layer, layers, csr, F, ef):
-        self.layer, self.layers, self.csr, self.F, self.ef = layer, layers, csr, F, ef
-        self.ws = None
+        self.layer, self.csr, self.F, self.ef = layer, csr, F, ef
         d = L.MswSwegnnTrainDesc()
         d.num_nodes, d.num_edges = csr.num_nodes, csr.num_edges
-        d.F, d.edge_features, d.K, d.n_layers = F, ef, layer.K, len(layers)
-        d.width[0] = layers[0][0].in_features
-        for i, (lin, act) in enumerate(layers):
-            d.width[i + 1] = lin.out_features
-            d.act[i] = _act_code(act)
+        d.F, d.edge_features, d.K = F, ef, layer.K
         d.normalize = int(bool(layer.normalize))
         d.with_filter_matrix = int(bool(layer.with_filter_matrix))
         d.with_gradient = int(bool(layer.with_gradient))
         d.upwind_mode = int(bool(layer.upwind_mode))
         for name in ("row", "col", "in_ptr", "in_edge", "out_ptr", "out_edge"):
             setattr(d, name, getattr(csr, name).data_ptr())
-        self.desc = d
-        # parameter list order = the Function's *params
-        self.params = []
-        for lin, act in layers:
-            self.params.append(lin.weight)
-            if lin.bias is not None:
-                self.params.append(lin.bias)
-            if isinstance(act, nn.PReLU):
-                self.params.append(act.weight)
-        if layer.with_filter_matrix:
-            self.params += [f.weight for f in layer.filter_matrix]
-
-    def bind(self, params):
-        """Point the descriptor at the (contiguous) parameter tensors of this call."""
-        d, it = self.desc, iter(params)
-        for i, (lin, act) in enumerate(self.layers):
-            d.weight[i] = next(it).data_ptr()
-            d.bias[i] = next(it).data_ptr() if lin.bias is not None else None
-            d.slope[i] = next(it).data_ptr() if isinstance(act, nn.PReLU) else None
-        if self.layer.with_filter_matrix:
-            for k in range(self.layer.K + 1):
-                d.filter[k] = next(it).data_ptr()
-        return d
+        super().__init__(layers, d, "msw_swegnn_train_workspace", layer)
 
 
-def _ws(meta):
-    if meta.ws is None:  # depends on the descriptor's sizes only
-        s, t = C.c_int64(), C.c_int64()
-        L.check(L.lib().msw_swegnn_train_workspace(C.byref(meta.desc), C.byref(s), C.byref(t)))
-        meta.ws = int(s.value), int(t.value)
-    return meta.ws
+class _MlpMeta(_StackMeta):
+    def __init__(self, layers, rows):
+        d = L.MswMlpTrainDesc()
+        d.rows = rows
+        super().__init__(layers, d, "msw_mlp_train_workspace")
 
 
 _META_CACHE = OrderedDict()
@@ -283,7 +322,7 @@ class _SwegnnFunction(torch.autograd.Function):
         ea = edge_attr.contiguous() if meta.ef > 0 else None
         params = [p.contiguous() for p in params]
         d = meta.bind(params)
-        n_saved, _ = _ws(meta)
+        n_saved, _ = meta.sizes()
         saved = torch.empty(n_saved, device=dev, dtype=torch.float32)
         out = torch.empty(meta.csr.num_nodes, meta.F, device=dev, dtype=torch.float32)
         with torch.cuda.device(dev):  # the kernels launch on the current device
@@ -306,7 +345,7 @@ class _SwegnnFunction(torch.autograd.Function):
         dev = x_d.device
         gout = gout.contiguous().to(torch.float32)
         d = meta.bind(params)
-        _, n_scratch = _ws(meta)
+        _, n_scratch = meta.sizes()
         scratch = torch.empty(n_scratch, device=dev, dtype=torch.float32)
         g = L.MswSwegnnGrads()
         dxs = torch.empty_like(x_s) if ctx.needs_input_grad[1] else None
@@ -316,20 +355,7 @@ class _SwegnnFunction(torch.autograd.Function):
         g.d_x_d = dxd.data_ptr()
         g.d_edge_attr = dea.data_ptr() if dea is not None else None
         dps = [torch.empty_like(p) if ctx.needs_input_grad[4 + i] else None for i, p in enumerate(params)]
-        it = iter(dps)
-        for i, (lin, act) in enumerate(meta.layers):
-            w = next(it)
-            g.d_weight[i] = w.data_ptr() if w is not None else None
-            if lin.bias is not None:
-                b = next(it)
-                g.d_bias[i] = b.data_ptr() if b is not None else None
-            if isinstance(act, nn.PReLU):
-                a = next(it)
-                g.d_slope[i] = a.data_ptr() if a is not None else None
-        if meta.layer.with_filter_matrix:
-            for k in range(meta.layer.K + 1):
-                f = next(it)
-                g.d_filter[k] = f.data_ptr() if f is not None else None
+        meta.bind_grads(g, dps)
         with torch.cuda.device(dev):  # the kernels launch on the current device
             L.check(L.lib().msw_swegnn_train_backward(C.byref(d), x_s.data_ptr(), x_d.data_ptr(),
                                                       ea.data_ptr() if meta.ef > 0 else None, saved.data_ptr(),
@@ -363,41 +389,6 @@ def mlp_supported(seq, x):
     return all(p.dtype == torch.float32 and p.is_cuda for p in seq.parameters())
 
 
-class _MlpMeta:
-    def __init__(self, layers, rows):
-        self.layers = layers
-        self.ws = None
-        d = L.MswMlpTrainDesc()
-        d.rows, d.n_layers = rows, len(layers)
-        d.width[0] = layers[0][0].in_features
-        for i, (lin, act) in enumerate(layers):
-            d.width[i + 1] = lin.out_features
-            d.act[i] = _act_code(act)
-        self.desc = d
-        self.params = []
-        for lin, act in layers:
-            self.params.append(lin.weight)
-            if lin.bias is not None:
-                self.params.append(lin.bias)
-            if isinstance(act, nn.PReLU):
-                self.params.append(act.weight)
-
-    def bind(self, params):
-        d, it = self.desc, iter(params)
-        for i, (lin, act) in enumerate(self.layers):
-            d.weight[i] = next(it).data_ptr()
-            d.bias[i] = next(it).data_ptr() if lin.bias is not None else None
-            d.slope[i] = next(it).data_ptr() if isinstance(act, nn.PReLU) else None
-        return d
-
-    def workspace(self):
-        if self.ws is None:
-            s, t = C.c_int64(), C.c_int64()
-            L.check(L.lib().msw_mlp_train_workspace(C.byref(self.desc), C.byref(s), C.byref(t)))
-            self.ws = int(s.value), int(t.value)
-        return self.ws
-
-
 class _MlpFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, meta, x, *params):
@@ -405,7 +396,7 @@ class _MlpFunction(torch.autograd.Function):
         x = x.contiguous()
         params = [p.contiguous() for p in params]
         d = meta.bind(params)
-        n_saved, _ = meta.workspace()
+        n_saved, _ = meta.sizes()
         saved = torch.empty(max(n_saved, 1), device=dev, dtype=torch.float32)
         out = torch.empty(x.shape[0], meta.layers[-1][0].out_features, device=dev, dtype=torch.float32)
         with torch.cuda.device(dev):  # the kernels launch on the current device
@@ -425,22 +416,13 @@ class _MlpFunction(torch.autograd.Function):
         dev = x.device
         gout = gout.contiguous().to(torch.float32)
         d = meta.bind(params)
-        _, n_scratch = meta.workspace()
+        _, n_scratch = meta.sizes()
         scratch = torch.empty(max(n_scratch, 1), device=dev, dtype=torch.float32)
         g = L.MswMlpGrads()
         dx = torch.empty_like(x) if ctx.needs_input_grad[1] else None
         g.d_x = dx.data_ptr() if dx is not None else None
         dps = [torch.empty_like(p) if ctx.needs_input_grad[2 + i] else None for i, p in enumerate(params)]
-        it = iter(dps)
-        for i, (lin, act) in enumerate(meta.layers):
-            w = next(it)
-            g.d_weight[i] = w.data_ptr() if w is not None else None
-            if lin.bias is not None:
-                b = next(it)
-                g.d_bias[i] = b.data_ptr() if b is not None else None
-            if isinstance(act, nn.PReLU):
-                a = next(it)
-                g.d_slope[i] = a.data_ptr() if a is not None else None
+        meta.bind_grads(g, dps)
         with torch.cuda.device(dev):  # the kernels launch on the current device
             L.check(L.lib().msw_mlp_train_backward(C.byref(d), x.data_ptr(), saved.data_ptr(), gout.data_ptr(),
                                                    C.byref(g), scratch.data_ptr(),

@@ -128,6 +128,62 @@ def test_training_abi_validation_and_workspace_without_gpu(libso):
     assert lib.msw_pool_mean_backward(5, 32, None, None, None, None, None, None, None) != 0
 
 
+def train_layout_table():
+    """(label, descriptor) of the training descriptors whose workspace sizes are pinned (below, and
+    recorded by tools/train_record.py).  MLP: depth 1..4 x rows 0, 1, 100, 129, 32769, the widths
+    taken in turn from 1, 63, 64, 65, 300, 9, 32.  SWEGNN: F x edge_features x K x depth over an
+    odd-sized graph (E = 37, N = 23: no multiple of 64 among E w, E, N F, K N unless a width
+    is one), the graph of tests/train_cases.py, a graph without edges and an empty one."""
+    from mswegnn import _lib as L
+    table, pool = [], (1, 63, 64, 65, 300, 9, 32)
+    for depth in range(1, 5):
+        for r, rows in enumerate((0, 1, 100, 129, 32769)):
+            d = L.MswMlpTrainDesc()
+            d.rows, d.n_layers = rows, depth
+            for i in range(depth + 1):
+                d.width[i] = pool[(2 * depth + r + i) % len(pool)]
+            for i in range(depth):
+                d.weight[i] = 16  # any non-null address: the workspace call only validates
+            table.append((f"mlp depth {depth} rows {rows} widths {list(d.width[:depth + 1])}", d))
+    for F in (1, 16, 50, 64):
+        for ef in (0, 1, 32):
+            for K in (1, 8):
+                for depth in range(1, 5):
+                    for E, N in ((37, 23), (640, 203), (0, 203), (0, 0)):
+                        d = L.MswSwegnnTrainDesc()
+                        d.num_nodes, d.num_edges, d.F, d.edge_features, d.K, d.n_layers = N, E, F, ef, K, depth
+                        for i, w in enumerate([4 * F + ef] + [2 * F] * (depth - 1) + [F]):
+                            d.width[i] = w
+                        table.append((f"swegnn F {F} ef {ef} K {K} depth {depth} E {E} N {N}", d))
+    return table
+
+
+def test_training_saved_layout_restatement_matches_library(libso):
+    """mswegnn/autograd.py reads the saved buffers by offsets it restates from csrc/train.hip
+    (_mlp_offsets, _swegnn_offsets): the end offset of each restatement is the library's
+    saved_floats for every descriptor of the table -- depths, empty and odd row counts, widths
+    around the 64-float slot, graphs without edges or nodes."""
+    from mswegnn import _lib as L
+    from mswegnn import autograd as ag
+    lib = L.lib()
+    table = train_layout_table()
+    mlps = [d for _, d in table if isinstance(d, L.MswMlpTrainDesc)]
+    assert {1, 63, 64, 65, 300} <= {d.width[i] for d in mlps for i in range(d.n_layers + 1)}
+    assert {(d.n_layers, d.rows) for d in mlps} == {(n, r) for n in (1, 2, 3, 4) for r in (0, 1, 100, 129, 32769)}
+    odd = [d for _, d in table if isinstance(d, L.MswSwegnnTrainDesc) and d.num_edges == 37
+           and all(n % 64 for n in [d.num_edges, d.num_nodes * d.F, d.K * d.num_nodes]
+                   + [d.num_edges * d.width[i] for i in range(d.n_layers + 1)])]
+    assert len(odd) >= 64, len(odd)
+    for label, d in table:
+        s, t = C.c_int64(-1), C.c_int64(-1)
+        mlp = isinstance(d, L.MswMlpTrainDesc)
+        fn = lib.msw_mlp_train_workspace if mlp else lib.msw_swegnn_train_workspace
+        assert fn(C.byref(d), C.byref(s), C.byref(t)) == 0, (label, lib.msw_last_error())
+        off = ag._mlp_offsets(d) if mlp else ag._swegnn_offsets(d)
+        assert s.value == off["end"], (label, s.value, off)
+        assert t.value > 0 and len(off["pre"]) == d.n_layers, label
+
+
 def test_training_descriptor_cache_keys_follow_parameters():
     """mswegnn/autograd.py reuses a layer's descriptor template while the layer holds the same
     parameter objects: the validation list (_param_list) is the descriptor's own binding order

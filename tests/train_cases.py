@@ -21,8 +21,8 @@ is the only rounding -- the one the kernels perform.  Pooling: every child of a 
 children holds a multiple of c and grad_out[parent] is a multiple of c, so the quotients are
 exact too.
 
-The launch rules the cases aim at (csrc/train.hip, bottom: gemm, weight_grad, splits_for,
-blocks_for, mlp_backward) are restated below (``splits_for`` ... ``CAP``) only to place the cases
+The launch rules the cases aim at (csrc/train.hip, host part: gemm, weight_grad, splits_for and
+split_k, blocks_for, mlp_backward) are restated below (``splits_for`` ... ``CAP``) only to place the cases
 and to give the wrong variants their meaning; the correct restatement never reads them.
 
 Each wrong ``variant`` must change a compared tensor on its named case
