@@ -184,6 +184,27 @@ int msw_plan_destroy(msw_plan* plan);
 int msw_plan_create_part(const msw_graph_desc* graph, const msw_model_desc* model, int device,
                          const msw_exchange_desc* xch, int32_t rank, msw_plan** out_plan);
 
+/* msw_plan_create with a base row order.  A plan keeps the caller's numbering at every boundary
+ * (x, y, the rollout's out, node_bc, msw_debug_buffer) and lays each (graph, scale) range of
+ * node_ptr out internally in graph order, moved only inside tiling.h's 64-row packing window, so
+ * every row gather of the step inherits the caller's numbering.  row_order (HOST int64
+ * [num_nodes], read during the call only) replaces the graph order: over every range [a, b) that
+ * node_ptr names, row_order[a .. b) must be a permutation of a .. b-1, and the range's rows are
+ * laid out in that order before the packing runs (on the in-degrees taken in that order).  No sum
+ * changes its terms or their order, so the plan gives the bits of msw_plan_create's plan, in the
+ * caller's numbering (msw_locality_order below builds such an order from coordinates).
+ * row_order NULL: exactly msw_plan_create.
+ * MSW_ERR_INVALID, naming the first offending position of row_order (ranges in node_ptr's order):
+ * an entry outside its range (so an entry that crosses a scale or a graph), a repeated entry.
+ * Partitioned plans (msw_plan_create_part) take no order. */
+int msw_plan_create_ordered(const msw_graph_desc* graph, const msw_model_desc* model, int device,
+                            const int64_t* row_order, msw_plan** out_plan);
+
+/* The plan's internal row layout: perm[i] = graph row held by internal row i, -1 for a padding
+ * row (scale starts are padded).  Writes min(capacity, npad) entries to perm (HOST) and the number
+ * of internal rows to *npad; capacity = 0 (perm may be NULL) sizes the buffer.  Host only. */
+int msw_plan_row_layout(const msw_plan* plan, int32_t* perm, int64_t capacity, int64_t* npad);
+
 /* RCCL transport.  msw_comm_unique_id writes an ncclUniqueId (128 bytes) on the rank that
  * creates it; every rank then calls msw_plan_set_comm with the same bytes.  RCCL is bound
  * at run time from the process (the copy PyTorch loaded) or librccl.so.1. */
@@ -769,6 +790,54 @@ int msw_mesh_dual_get_stats(const msw_mesh_dual* dual, msw_mesh_dual_stats* stat
  * 64 consecutive faces per round, at most 4096 workgroups, grid * 64 * iters >= num_faces.
  * num_faces = 0: grid and iters are 0.  MSW_ERR_INVALID: a NULL output, num_faces negative. */
 int msw_mesh_dual_launch(int64_t num_faces, int32_t* grid, int32_t* faces_per_wg, int32_t* iters);
+
+/* Locality order: a row order for msw_plan_create_ordered from per-row coordinates, rows sorted
+ * along a Hilbert curve inside each segment (a (graph, scale) range).
+ *
+ * Keys.  With the segment's box (x0, y0, side): sc = 65536.0 / side, fx = (x - x0) * sc,
+ *     ix = fx < 0 ? 0 : fx >= 65536 ? 65535 : (int)floor(fx),          fy, iy likewise,
+ * each a separate IEEE float64 operation (nothing contracts), and the key is the 32-bit index of
+ * cell (ix, iy) on the order-16 Hilbert curve:
+ *     d = 0;  for (s = 32768; s > 0; s >>= 1) {
+ *         rx = (ix & s) != 0;  ry = (iy & s) != 0;  d += s * s * ((3 * rx) ^ ry);
+ *         if (!ry) { if (rx) { ix = 65535 - ix; iy = 65535 - iy; }  swap(ix, iy); } }
+ * A row with a non-finite coordinate gets key 0xFFFFFFFF (it sorts last, with the curve's last cell).
+ * Order.  Inside segment j, order[seg_ptr[j] + k] is the row of [seg_ptr[j], seg_ptr[j + 1]) with
+ * the k-th smallest key, ties to the lower row: a stable sort, so no output bit depends on an order
+ * of execution (LSD radix sort of (key, row) pairs, 8-bit digits, LDS counters, no global atomics;
+ * the segment index is sorted last as further digits).
+ *
+ * msw_locality_order: xy device float64 [n][2], seg_ptr HOST int64 [num_segs + 1] tiling [0, n)
+ * (empty segments allowed), boxes HOST float64 [num_segs][3] = (x0, y0, side), order device int32
+ * [n].  Host-synchronous: allocates its scratch (12 bytes per row and the digit table), runs on
+ * `stream`, waits for it and frees.  stats may be NULL.  n = 0: no-op.
+ * msw_hilbert_keys: the key kernel alone with one box, keys device uint32 [n]; stream-ordered, no
+ * allocation.  msw_locality_sort: the sort alone on given keys (device uint32 [n]); otherwise as
+ * msw_locality_order.
+ * MSW_ERR_INVALID (before any HIP call): NULLs, negative n, num_segs < 1, a seg_ptr that does not
+ * tile [0, n), a box that is not finite, a side that is not finite and positive or so small that
+ * 65536.0 / side is not finite, xy not 8-byte or keys / order not 4-byte aligned.  MSW_ERR_UNSUPPORTED: n > 2^26 (from the size alone). */
+typedef struct {
+  int64_t n, num_segs;
+  int64_t scratch_bytes;      /* device memory allocated and freed by the call                      */
+  int32_t passes;             /* radix passes: 4 over the key + those over the segment index        */
+  int32_t grid;               /* workgroups of every launch of the sort                             */
+  double  keys_us, sort_us;   /* device time of the key kernel and of all sort passes (events)      */
+} msw_locality_stats;
+
+int msw_locality_order(const double* xy, int64_t n, const int64_t* seg_ptr, int32_t num_segs,
+                       const double* boxes, int32_t* order, int device, void* stream,
+                       msw_locality_stats* stats);
+int msw_hilbert_keys(const double* xy, int64_t n, double x0, double y0, double side, uint32_t* keys,
+                     void* stream);
+int msw_locality_sort(const uint32_t* keys, int64_t n, const int64_t* seg_ptr, int32_t num_segs,
+                      int32_t* order, int device, void* stream, msw_locality_stats* stats);
+/* The launch of the key kernel and of every pass of the sort over n rows (from the code the
+ * launchers themselves use): 256-thread workgroups, items_per_wg = 256 consecutive rows per round,
+ * at most 1024 workgroups, each taking `iters` consecutive rounds (the sort: one contiguous run),
+ * grid * 256 * iters >= n.  n = 0: grid and iters are 0.
+ * MSW_ERR_INVALID: a NULL output, n negative.  Host only. */
+int msw_locality_launch(int64_t n, int32_t* grid, int32_t* items_per_wg, int32_t* iters);
 
 /* ---- Training: autograd through one SWEGNN processor ------------------------
  * Replaces the autograd of SWEGNN.forward (models/gnn.py:387-445) the reference trains through

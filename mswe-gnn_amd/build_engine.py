@@ -21,7 +21,7 @@ SRC = ["csrc/kernels_nt1.hip", "csrc/kernels_nt2.hip", "csrc/kernels_nt4.hip",
        "csrc/kernels_common.hip", "csrc/plan.hip", "csrc/weights.hip", "csrc/schedule.hip", "csrc/runtime.hip",
        "csrc/metrics.hip", "csrc/floodmaps.hip", "csrc/series.hip",
        "csrc/train.hip", "csrc/loss.hip", "csrc/ensemble.hip", "csrc/scores.hip", "csrc/raster.hip",
-       "csrc/zonal.hip", "csrc/meshgraph.hip"]
+       "csrc/zonal.hip", "csrc/meshgraph.hip", "csrc/locality.hip"]
 # every header under csrc/, in sorted order: a header left out would mean a stale library that
 # reports itself current (the staleness check and source_hash() go by this list)
 HDR = [os.path.join(ROOT, "include", "mswegnn.h")]

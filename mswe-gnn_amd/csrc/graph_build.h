@@ -209,10 +209,13 @@ inline std::vector<LaneRec> make_recs(const std::vector<int>& rowptr, const std:
 // The whole host graph plan.  align: scale starts are padded to multiples of this many rows
 // (the encoder's workgroup rows: a workgroup never straddles two scales); pack: destinations
 // in tiling.h pack_order (else graph order); row_min_tiles: scales with at least this many
-// edge tiles get the row-layout CSR (0: every scale).  Returns MSW_OK or an MSW_ERR_* code
-// with `err` set.
+// edge tiles get the row-layout CSR (0: every scale).  row_order (msw_plan_create_ordered; NULL:
+// graph order): host [num_nodes], over every range [a, b) of node_ptr a permutation of a..b-1, the
+// order in which the range's rows are laid out before pack_order runs (its in-degrees follow that
+// order); an entry outside its range or a repeated one is refused with the first such position
+// named.  Returns MSW_OK or an MSW_ERR_* code with `err` set.
 inline int build_host_graph(const msw_graph_desc* g, int S, int align, bool pack, int row_min_tiles, HostGraph& H,
-                            std::string& err) {
+                            std::string& err, const int64_t* row_order = nullptr) {
   auto bad = [&](int code, const std::string& m) {
     err = m;
     return code;
@@ -239,6 +242,35 @@ inline int build_host_graph(const msw_graph_desc* g, int S, int align, bool pack
       const int64_t cl = g->edge_index[g->num_edges + e];
       if (cl >= 0 && cl < N) ++indeg[cl];
     }
+  if (row_order) {  // checked whole, ranges in node_ptr's order, before any entry is used
+    // node_ptr first: over ranges that overlap, a correct order would be reported as repeating
+    std::vector<char> seen(N, 0);
+    for (int gi = 0; gi < G; ++gi)
+      for (int s = 0; s < S; ++s) {
+        const int64_t a = g->node_ptr[gi * (S + 1) + s], b = g->node_ptr[gi * (S + 1) + s + 1];
+        if (a < 0 || b < a || b > N) return bad(MSW_ERR_INVALID, "node_ptr out of range");
+        for (int64_t v = a; v < b; ++v) {
+          if (seen[v]) return bad(MSW_ERR_INVALID, "node_ptr ranges overlap");
+          seen[v] = 1;
+        }
+      }
+    std::fill(seen.begin(), seen.end(), 0);
+    auto at = [&](int64_t v) { return "row_order[" + std::to_string(v) + "] = " + std::to_string(row_order[v]); };
+    for (int gi = 0; gi < G; ++gi)
+      for (int s = 0; s < S; ++s) {
+        const int64_t a = g->node_ptr[gi * (S + 1) + s], b = g->node_ptr[gi * (S + 1) + s + 1];
+        for (int64_t v = a; v < b; ++v) {
+          const int64_t r = row_order[v];
+          if (r < a || r >= b)
+            return bad(MSW_ERR_INVALID, at(v) + " lies outside its range [" + std::to_string(a) + ", " +
+                                            std::to_string(b) + ") (graph " + std::to_string(gi) + ", scale " +
+                                            std::to_string(s) + ")");
+          if (seen[r]) return bad(MSW_ERR_INVALID, at(v) + " repeats an earlier entry");
+          seen[r] = 1;
+        }
+      }
+  }
+  auto row_at = [&](int64_t v) { return row_order ? row_order[v] : v; };
   int64_t placed = 0;
   for (int s = 0; s < S; ++s) {
     H.sc[s].n0 = (int)H.perm.size();
@@ -248,10 +280,10 @@ inline int build_host_graph(const msw_graph_desc* g, int S, int align, bool pack
       if ((placed += b - a) > N) return bad(MSW_ERR_INVALID, "node_ptr ranges overlap");
       if (pack) {
         std::vector<int> d((size_t)(b - a));
-        for (int64_t v = a; v < b; ++v) d[v - a] = indeg[v];
-        for (int k : pack_order(d)) H.perm.push_back((int)(a + k));
+        for (int64_t v = a; v < b; ++v) d[v - a] = indeg[row_at(v)];
+        for (int k : pack_order(d)) H.perm.push_back((int)row_at(a + k));
       } else {
-        for (int64_t v = a; v < b; ++v) H.perm.push_back((int)v);
+        for (int64_t v = a; v < b; ++v) H.perm.push_back((int)row_at(v));
       }
     }
     H.sc[s].ns = (int)H.perm.size() - H.sc[s].n0;

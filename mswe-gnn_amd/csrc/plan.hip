@@ -17,12 +17,12 @@ namespace {
 
 thread_local std::string g_err;
 
-int build_graph_plan(msw_plan* P, const msw_graph_desc* g) {
+int build_graph_plan(msw_plan* P, const msw_graph_desc* g, const int64_t* row_order) {
   // the host plan (graph_build.h: numbering, CSRs, tiles, records -- also built by the
   // sanitizer harness tests/asan/host_plan_check.cpp), then its device copies
   HostGraph H;
   std::string err;
-  int rc = build_host_graph(g, P->S, kRowsPerBlock, P->kn.tile_pack != 0, row_hop_min_tiles(P), H, err);
+  int rc = build_host_graph(g, P->S, kRowsPerBlock, P->kn.tile_pack != 0, row_hop_min_tiles(P), H, err, row_order);
   if (rc) return fail(rc, err);
   P->N = H.N;
   P->E = H.E;
@@ -220,7 +220,7 @@ int static_edge_features(msw_plan* P, const msw_graph_desc* g, const msw_model_d
 }
 
 int plan_create_impl(const msw_graph_desc* g, const msw_model_desc* m, int device,
-                     const msw_exchange_desc* xch, int rank, msw_plan** out_plan) {
+                     const msw_exchange_desc* xch, int rank, const int64_t* row_order, msw_plan** out_plan) {
   if (!g || !m || !out_plan) return fail(MSW_ERR_INVALID, "null argument");
   *out_plan = nullptr;
   if (m->model_type != 0 && m->model_type != 1) return fail(MSW_ERR_INVALID, "model_type must be 0 (MSGNN) or 1 (GNN)");
@@ -237,7 +237,7 @@ int plan_create_impl(const msw_graph_desc* g, const msw_model_desc* m, int devic
   if ((rc = check_model(P.get(), m))) return rc;
   P->kn = knobs_from_env(P->NT);
   P->part_rank = xch ? rank : -1;
-  if ((rc = build_graph_plan(P.get(), g))) return rc;
+  if ((rc = build_graph_plan(P.get(), g, row_order))) return rc;
   if (xch && (rc = build_exchange(P.get(), xch))) return rc;
   if ((rc = pack_model(P.get(), m, g->num_edge_features))) return rc;
   if ((rc = alloc_buffers(P.get()))) return rc;
@@ -270,7 +270,8 @@ int64_t msw_struct_size(const char* name) {
       MSW_SIZE(msw_mlp_grads), MSW_SIZE(msw_flood_maps), MSW_SIZE(msw_zone_series),
       MSW_SIZE(msw_train_loss_desc), MSW_SIZE(msw_ensemble_steps_out), MSW_SIZE(msw_ensemble_maps_out),
       MSW_SIZE(msw_ensemble_scores_out), MSW_SIZE(msw_raster_grid), MSW_SIZE(msw_raster_stats),
-      MSW_SIZE(msw_zonal_stats), MSW_SIZE(msw_locator_stats), MSW_SIZE(msw_mesh_dual_stats)};
+      MSW_SIZE(msw_zonal_stats), MSW_SIZE(msw_locator_stats), MSW_SIZE(msw_mesh_dual_stats),
+      MSW_SIZE(msw_locality_stats)};
 #undef MSW_SIZE
   for (const auto& t : tab)
     if (name && !strcmp(name, t.name)) return t.size;
@@ -280,7 +281,12 @@ int64_t msw_struct_size(const char* name) {
 int msw_abi_version(void) { return MSW_ABI_VERSION; }
 
 int msw_plan_create(const msw_graph_desc* g, const msw_model_desc* m, int device, msw_plan** out_plan) {
-  return plan_create_impl(g, m, device, nullptr, -1, out_plan);
+  return plan_create_impl(g, m, device, nullptr, -1, nullptr, out_plan);
+}
+
+int msw_plan_create_ordered(const msw_graph_desc* g, const msw_model_desc* m, int device, const int64_t* row_order,
+                            msw_plan** out_plan) {
+  return plan_create_impl(g, m, device, nullptr, -1, row_order, out_plan);
 }
 
 int msw_plan_create_part(const msw_graph_desc* g, const msw_model_desc* m, int device,
@@ -289,7 +295,7 @@ int msw_plan_create_part(const msw_graph_desc* g, const msw_model_desc* m, int d
   if (xch->num_entries < 0 || (xch->num_entries > 0 && (!xch->peer || !xch->scale || !xch->recv_ptr ||
                                                          !xch->send_ptr)))
     return fail(MSW_ERR_INVALID, "exchange descriptor arrays missing");
-  return plan_create_impl(g, m, device, xch, rank, out_plan);
+  return plan_create_impl(g, m, device, xch, rank, nullptr, out_plan);
 }
 
 int msw_plan_destroy(msw_plan* plan) {
@@ -317,6 +323,13 @@ int msw_debug_buffer(msw_plan* P, const char* name, float* dst, void* stream) {
     if (P->perm[i] >= 0)
       std::copy(h.begin() + (size_t)i * P->Fp, h.begin() + (size_t)i * P->Fp + P->F, o.begin() + (size_t)P->perm[i] * P->F);
   HIP_TRY(hipMemcpy(dst, o.data(), o.size() * sizeof(float), hipMemcpyHostToDevice));
+  return MSW_OK;
+}
+
+int msw_plan_row_layout(const msw_plan* P, int32_t* perm, int64_t capacity, int64_t* npad) {
+  if (!P || !npad || capacity < 0 || (capacity > 0 && !perm)) return fail(MSW_ERR_INVALID, "bad argument");
+  *npad = P->Npad;
+  std::copy(P->perm.begin(), P->perm.begin() + std::min<int64_t>(capacity, P->Npad), perm);
   return MSW_OK;
 }
 

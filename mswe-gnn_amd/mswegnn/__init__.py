@@ -9,7 +9,8 @@ on-device metrics (``metrics``), on-device flood maps and chunked rollouts (``fl
 zone series (``series``), on-device ensemble products and the
 scores of an ensemble against a truth run (``ensemble``), maps and rollout frames resampled
 onto regular grids (``raster``), multiscale graphs from plain triangulations and graph rows from
-(x, y) points (``meshgraph``), the training layers'
+(x, y) points (``meshgraph``), a locality row order for plans from per-row coordinates
+(``locality``), the training layers'
 autograd (``autograd``), the training loss (``loss``) and the synthetic meshes (``mesh``).
 """
 import os

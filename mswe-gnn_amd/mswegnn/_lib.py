@@ -173,6 +173,11 @@ class MswMeshDualStats(C.Structure):
                 ("faces_us", C.c_double), ("edges_us", C.c_double)]
 
 
+class MswLocalityStats(C.Structure):
+    _fields_ = [("n", C.c_int64), ("num_segs", C.c_int64), ("scratch_bytes", C.c_int64),
+                ("passes", C.c_int32), ("grid", C.c_int32), ("keys_us", C.c_double), ("sort_us", C.c_double)]
+
+
 MAX_LOSS_RANGES = 64
 TRAIN_LOSS_RECORD = 12
 LOSS_TYPE = {"RMSE": 0, "MAE": 1}
@@ -267,6 +272,15 @@ SYMBOLS = [
                                        c_int64_p, C.POINTER(C.c_void_p), c_int64_p]),
     ("msw_mesh_dual_get_stats", C.c_int, [C.c_void_p, C.POINTER(MswMeshDualStats)]),
     ("msw_mesh_dual_launch", C.c_int, [C.c_int64, c_int32_p, c_int32_p, c_int32_p]),
+    ("msw_locality_order", C.c_int, [C.c_void_p, C.c_int64, c_int64_p, C.c_int32, C.POINTER(C.c_double), C.c_void_p,
+                                     C.c_int, C.c_void_p, C.POINTER(MswLocalityStats)]),
+    ("msw_hilbert_keys", C.c_int, [C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
+    ("msw_locality_sort", C.c_int, [C.c_void_p, C.c_int64, c_int64_p, C.c_int32, C.c_void_p, C.c_int, C.c_void_p,
+                                    C.POINTER(MswLocalityStats)]),
+    ("msw_locality_launch", C.c_int, [C.c_int64, c_int32_p, c_int32_p, c_int32_p]),
+    ("msw_plan_create_ordered", C.c_int, [C.POINTER(MswGraphDesc), C.POINTER(MswModelDesc), C.c_int, c_int64_p,
+                                          C.POINTER(C.c_void_p)]),
+    ("msw_plan_row_layout", C.c_int, [C.c_void_p, c_int32_p, C.c_int64, c_int64_p]),
     ("msw_plan_create_part", C.c_int, [C.POINTER(MswGraphDesc), C.POINTER(MswModelDesc), C.c_int,
                                        C.POINTER(MswExchangeDesc), C.c_int32, C.POINTER(C.c_void_p)]),
     ("msw_comm_unique_id", C.c_int, [C.c_char_p]),
@@ -308,7 +322,7 @@ STRUCTS = {"msw_linear": MswLinear, "msw_mlp": MswMlp, "msw_swegnn": MswSwegnn,
            "msw_ensemble_scores_out": MswEnsembleScoresOut,
            "msw_raster_grid": MswRasterGrid, "msw_raster_stats": MswRasterStats,
            "msw_zonal_stats": MswZonalStats, "msw_locator_stats": MswLocatorStats,
-           "msw_mesh_dual_stats": MswMeshDualStats}
+           "msw_mesh_dual_stats": MswMeshDualStats, "msw_locality_stats": MswLocalityStats}
 
 _lib = None
 
@@ -342,6 +356,7 @@ def lib_info():
             "bytes": st.st_size, "mtime": st.st_mtime, "sha256": hashlib.sha256(data).hexdigest()}
 
 
+MSW_ERR_INVALID = -1
 MSW_ERR_UNSUPPORTED = -3
 
 

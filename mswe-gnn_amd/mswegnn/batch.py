@@ -46,6 +46,10 @@ def collate(graphs):
     for c in counts:
         offs.append(offs[-1] + c)
     for k in graphs[0].keys():
+        if k == "row_order":
+            # a member's plan layout (mswegnn.locality) is not a PyG attribute and is not carried:
+            # concatenated it would lack the members' offsets; compute the order on the batch
+            continue
         vals = [getattr(g, k) for g in graphs]
         if not isinstance(vals[0], torch.Tensor):
             setattr(b, k, vals)

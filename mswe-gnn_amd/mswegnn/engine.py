@@ -146,6 +146,8 @@ def _i64(keep, t):
 
 
 def describe_graph(model, graph):
+    """Graph -> (MswGraphDesc, keepalive list).  A base row order travels beside the descriptor:
+    ``getattr(graph, "row_order", None)``, see :func:`_row_order`."""
     keep = []
     g = L.MswGraphDesc()
     N = int(graph.x.shape[0])
@@ -182,6 +184,18 @@ def describe_graph(model, graph):
     return g, keep
 
 
+def _row_order(keep, graph):
+    """``graph.row_order`` (mswegnn.locality.row_order; absent or None: no order) as the host int64
+    array of msw_plan_create_ordered.  Its length is checked here, its content by the library."""
+    ro = getattr(graph, "row_order", None)
+    if ro is None:
+        return None
+    N = int(graph.x.shape[0])
+    if ro.dim() != 1 or int(ro.shape[0]) != N:
+        raise L.EngineError(L.MSW_ERR_INVALID, f"row_order has shape {tuple(ro.shape)}, the graph has {N} rows")
+    return _i64(keep, ro)
+
+
 # ------------------------------------------------------------------ plan
 class EnginePlan:
     """An msw_plan: the graph (CSR per scale, pooling maps) and packed weights on one GPU."""
@@ -197,10 +211,15 @@ class EnginePlan:
         self.previous_t = int(model.previous_t)
         md, k1 = describe_model(model)
         gd, k2 = describe_graph(model, graph)
+        order = _row_order(k2, graph)
+        if order is not None and exchange is not None:
+            raise ValueError("a partitioned plan takes no row order (graph.row_order with an exchange)")
         h = C.c_void_p()
         lib = L.lib()
         dev = self.device.index or 0
-        if exchange is None:
+        if order is not None:
+            L.check(lib.msw_plan_create_ordered(C.byref(gd), C.byref(md), dev, order, C.byref(h)))
+        elif exchange is None:
             L.check(lib.msw_plan_create(C.byref(gd), C.byref(md), dev, C.byref(h)))
         else:
             L.check(lib.msw_plan_create_part(C.byref(gd), C.byref(md), dev, C.byref(exchange), int(rank),
@@ -307,6 +326,15 @@ class EnginePlan:
         out = {k: getattr(s, k) for k, _ in L.MswPlanStats._fields_}
         return out
 
+    def row_layout(self):
+        """The plan's internal row layout (msw_plan_row_layout): int32 numpy [Npad], the graph row
+        held by each internal row, -1 for a padding row."""
+        npad = C.c_int64(0)
+        L.check(L.lib().msw_plan_row_layout(self._h, None, 0, C.byref(npad)))
+        perm = np.empty(npad.value, dtype=np.int32)
+        L.check(L.lib().msw_plan_row_layout(self._h, perm.ctypes.data_as(L.c_int32_p), npad.value, C.byref(npad)))
+        return perm
+
     def schedule(self, rollout=True):
         """The launches of one rollout step (or of one forward), in order: a list of dicts
         with `kind`, `variant` (the kernel instantiation, e.g. "hop loop mid"), `nt`, `scale`,
@@ -329,19 +357,28 @@ _TOPOLOGY = {"GNN": ("edge_index", "edge_attr"),
                        "intra_edge_ptr")}
 
 
+def _identity(model, graph):
+    """The tensors that decide a plan's content: the topology, and ``row_order`` when the graph
+    carries one (a graph without the attribute gives the topology alone, as ever)."""
+    ts = tuple(getattr(graph, n) for n in _TOPOLOGY[model.type_model])
+    ro = getattr(graph, "row_order", None)
+    return ts if ro is None else ts + (ro,)
+
+
 class _GraphRef:
     """The tensors a plan was built from, held by STRONG reference and compared by identity
     plus in-place version: a freed tensor's address can be reused by a new same-shaped
     tensor (caching allocator), so addresses alone cannot tell two graphs apart."""
 
     def __init__(self, model, graph):
-        self.tensors = tuple(getattr(graph, n) for n in _TOPOLOGY[model.type_model])
+        self.tensors = _identity(model, graph)
         self.versions = tuple(t._version for t in self.tensors)
         self.shape = (tuple(graph.x.shape), str(graph.x.device))
 
     def matches(self, model, graph):
-        ts = tuple(getattr(graph, n) for n in _TOPOLOGY[model.type_model])
+        ts = _identity(model, graph)
         return (self.shape == (tuple(graph.x.shape), str(graph.x.device))
+                and len(ts) == len(self.tensors)
                 and all(a is b for a, b in zip(ts, self.tensors))
                 and self.versions == tuple(t._version for t in ts))
 
@@ -355,8 +392,10 @@ class _GraphRef:
         rollout_test makes once per rollout, train.py:80): one device compare per tensor.
         Only meaningful while the held tensors are unmodified (``still_valid``): a held
         tensor edited in place no longer shows the content the plan was built from."""
-        ts = tuple(getattr(graph, n) for n in _TOPOLOGY[model.type_model])
+        ts = _identity(model, graph)
         if self.shape != (tuple(graph.x.shape), str(graph.x.device)) or not self.still_valid():
+            return False
+        if len(ts) != len(self.tensors):  # one graph carries a row order, the other none
             return False
         for a, b in zip(ts, self.tensors):
             if a.shape != b.shape or a.dtype != b.dtype:
@@ -365,7 +404,7 @@ class _GraphRef:
 
     def adopt(self, model, graph):
         """Hold the new (equal) tensors so the next calls with them hit by identity."""
-        self.tensors = tuple(getattr(graph, n) for n in _TOPOLOGY[model.type_model])
+        self.tensors = _identity(model, graph)
         self.versions = tuple(t._version for t in self.tensors)
 
 

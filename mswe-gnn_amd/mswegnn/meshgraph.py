@@ -21,7 +21,9 @@ graphs on the host (``database/graph_creation.py``: meshkernel, networkx, and on
 
 Out of scope: mesh generation and refinement themselves, quadrilateral or polygonal faces, more
 than one BC edge per scale, the reference's ``get_slopes``, reading the reference's pickles, and any
-renumbering of the built graph -- it keeps the caller's face order.
+renumbering of the built graph -- it keeps the caller's face order.  A mesh numbered without
+locality need not run the engine's gathers without it: ``graph_from_meshes(..., locality=True)`` sets
+``graph.row_order`` (``mswegnn.locality``), the order in which a plan lays the rows out internally.
 
 On CPU tensors the same interface runs :func:`_locate_numpy` / :func:`_dual_numpy`, plain numpy
 restatements of the kernels.
@@ -373,6 +375,13 @@ class MeshGraph:
     def __init__(self, **kw):
         self.__dict__.update(kw)
 
+    @property
+    def row_xy(self):
+        """float64 [N, 2], one coordinate per graph row for ``mswegnn.locality.row_order``: each
+        face's centroid, each scale's ghost row at the centroid of its BC face (equal keys go to the
+        lower row, so the ghost follows that face)."""
+        return torch.cat([torch.cat([c, c[f:f + 1]]) for c, f in zip(self.centroids, self.bc_face)])
+
     def gauges(self, xy, scale=0):
         """Zones of one graph row per point, located in the faces of ``scale``."""
         g = self.graph
@@ -392,7 +401,7 @@ def _per_scale_dem(dem, nfs):
     return [d]
 
 
-def graph_from_meshes(scales, bc_xy, dem, previous_t=3, T=48, BC=None, type_BC=2, device="cpu"):
+def graph_from_meshes(scales, bc_xy, dem, previous_t=3, T=48, BC=None, type_BC=2, device="cpu", locality=False):
     """A multiscale graph in the reference's layout from plain triangulations.
 
     ``scales``: finest first, each ``(node_xy float64 [V, 2], face_nodes int32 [nf, 3])`` (what
@@ -405,6 +414,8 @@ def graph_from_meshes(scales, bc_xy, dem, previous_t=3, T=48, BC=None, type_BC=2
     that contains its centroid (none: ``ValueError`` with the count).  ``BC``: [nBC, previous_t,
     T + 1] (default: ``mswegnn.mesh.hydrograph_bc``).  ``device``: where the kernels run; the
     standardisation runs in numpy float64 on the host, and the graph is returned on the CPU.
+    ``locality=True`` also sets ``graph.row_order`` (``mswegnn.locality.row_order`` of
+    ``MeshGraph.row_xy``, computed on ``device``): the graph's arrays are the same either way.
 
     Layout (``mswegnn.mesh``): each scale's faces then its ghost row; each scale's dual edges
     sorted by (row, col) then the directed ghost -> BC-face edge; intra pairs coarse-major with the
@@ -523,9 +534,13 @@ def graph_from_meshes(scales, bc_xy, dem, previous_t=3, T=48, BC=None, type_BC=2
         area=torch.from_numpy(np.concatenate([d["area"] for d in sc]).astype(np.float32)),
         edge_BC_length=torch.tensor([d["bc_edge_len"] for d in sc], dtype=torch.float32),
     )
-    return MeshGraph(
+    out = MeshGraph(
         graph=graph, locators=[d["locator"] for d in sc], centroids=[torch.from_numpy(d["c"]) for d in sc],
         bc_face=[d["bc_face"] for d in sc], bc_edge=[d["bc_edge"] for d in sc],
         bc_point=[d["bc_point"] for d in sc], orphans=orphans, childless=childless,
         face_relative_distance=torch.from_numpy(rel),
         edge_slope=torch.from_numpy((dem_all[edge_index[0]] - dem_all[edge_index[1]]) / raw_len))
+    if locality:
+        from .locality import row_order
+        graph.row_order = row_order(graph, out.row_xy, device=device)
+    return out
